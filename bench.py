@@ -28,6 +28,17 @@ rank: weak scaling, no collective on the data path); ``--mode shard`` at N = 1 r
 sharded code path on one rank.  MC_BENCH_ONE_GPU=1 (rehearsal on a one-GPU box): every rank
 on GPU 0, each kernel on its share of the CUs, gloo for the host-side all-gathers.
 
+A plain run (``--gpus 1 --steps N --warmup W``) does only what the headline figure needs: set up,
+warm up, time the N steps, write ``--dump-outputs`` if asked, print the line.  ``--full`` adds
+what takes runs of its own: the rate on resident sequences, config D beside the config-B line
+(extra.config_d) and the reference on this host's cores (cpu_baseline); ``--no-cpu-baseline``,
+``--no-config-d``, ``--config-d-steps`` and ``--cpu-repeats`` trim a ``--full`` run.
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the last timed step computed,
+the partition its .clstr holds, as DIR/<name>.npy (float64 / float32, indexed by the read's
+position in the FASTA; see dump_outputs).  The FASTA depends on the arguments alone, so two
+builds run with the same arguments can be compared array for array.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -189,6 +200,64 @@ def kernel_pmc(kname):
     return round(e["hbm_bytes_per_dispatch"]) if e and "hbm_bytes_per_dispatch" in e else None
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(d, fasta, clstr):
+    """The partition of the last timed step's .clstr as arrays: per read (position in the FASTA)
+    ``cluster_id`` (the >Cluster number, -1: not in the file), ``member_rank`` (its line's index
+    within the cluster), ``length`` (the nt the line states), ``is_centre`` (float32: the line
+    ends in *); per cluster ``centre_read`` (the centre's read, -1: none marked) and
+    ``cluster_size``.  Past 64 MB in all, the per-read arrays hold a fixed sample of the reads
+    (seed 0, ascending; ``sample_index`` names them)."""
+    import numpy as np
+    index = {}
+    with open(fasta, "rb") as f:
+        for ln in f:
+            if ln.startswith(b">"):
+                index[ln[1:].rstrip(b"\r\n")] = len(index)
+    n = len(index)
+    cid = np.full(n, -1.0)
+    mrank = np.full(n, -1.0)
+    length = np.zeros(n)
+    centre = np.zeros(n, np.float32)
+    centre_read, size = [], []
+    with open(clstr, "rb") as f:
+        for ln in f:
+            if ln.startswith(b">Cluster"):
+                centre_read.append(-1.0)
+                size.append(0.0)
+                continue
+            if not ln.strip():
+                continue
+            pos, rest = ln.split(b"\t", 1)
+            nt, rest = rest.split(b"nt, >", 1)
+            hdr, tail = rest.rsplit(b"... ", 1)
+            i = index[hdr]
+            cid[i] = len(size) - 1
+            mrank[i] = int(pos)
+            length[i] = int(nt)
+            size[-1] += 1
+            if tail.strip() == b"*":
+                centre[i] = 1
+                centre_read[-1] = i
+    out = {"centre_read": np.array(centre_read, np.float64), "cluster_size": np.array(size, np.float64)}
+    per_read = {"cluster_id": cid, "member_rank": mrank, "length": length, "is_centre": centre}
+    fixed = sum(v.nbytes for v in out.values())
+    row = sum(v.itemsize for v in per_read.values()) + 8  # (+ its sample_index entry)
+    if fixed + n * row > DUMP_LIMIT_BYTES:
+        keep = max(0, (DUMP_LIMIT_BYTES - fixed) // row)
+        if keep == 0:  # (more clusters than the limit holds: a prefix of them, no reads)
+            out = {k: v[:DUMP_LIMIT_BYTES // 16] for k, v in out.items()}
+        pick = np.sort(np.random.default_rng(0).choice(n, size=min(n, keep), replace=False))
+        per_read = {k: v[pick] for k, v in per_read.items()}
+        per_read["sample_index"] = pick.astype(np.float64)
+    out.update(per_read)
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -204,12 +273,17 @@ def main():
     ap.add_argument("--mut", type=float, default=0.03)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--id", default="0.90")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: resident-sequence rate, config D beside config B "
+                         "(extra.config_d), the reference on this host (cpu_baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's partition as DIR/<name>.npy")
     ap.add_argument("--cpu-repeats", type=int, default=3, help="reference runs (median)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--stats-out", default=None)
     ap.add_argument("--keep-clstr", default=None, help="rank 0 keeps the last timed step's .clstr here")
     ap.add_argument("--config-d-steps", type=int, default=2,
-                    help="with the config-B line: also time config D (1M reads, BASELINE configs[3], the workload "
+                    help="--full, with the config-B line: also time config D (1M reads, BASELINE configs[3], the workload "
                          "that shards) at the same N, reported in extra.config_d (0: skip)")
     ap.add_argument("--no-config-d", action="store_true", help="same as --config-d-steps 0")
     a = ap.parse_args()
@@ -316,13 +390,13 @@ def main():
             el = float(t.item())
         return el, st, tm, first, res
 
-    elapsed, stats, tim, first_s, res_t = timed(fasta, a.steps, a.warmup, 2)
+    elapsed, stats, tim, first_s, res_t = timed(fasta, a.steps, a.warmup, 2 if a.full else 0)
     keep_src = last_clstr[0]
 
     # config D at the same N (the workload that shards by record: BASELINE configs[3]), so the
     # driver's 1 -> 8 GPU runs carry a config-D curve beside the config-B headline
     d_run = None
-    d_steps = 0 if a.no_config_d or a.workload != "B" or replicas else a.config_d_steps
+    d_steps = 0 if not a.full or a.no_config_d or a.workload != "B" or replicas else a.config_d_steps
     if d_steps > 0:
         dn, dt_, ds_ = WORKLOADS["D"]
         if rank == 0:
@@ -440,7 +514,7 @@ def main():
     if nwc:
         nw_roof["counters"] = nwc
     cpu = cpu_v3 = None
-    if not a.no_cpu_baseline and world == 1 and mode == "single" and a.workload == "B":
+    if a.full and not a.no_cpu_baseline and world == 1 and mode == "single" and a.workload == "B":
         # the reference: rank 0 at N = 1 only, on the full config-B FASTA (~27 s a run)
         cpu = cpu_baseline(fasta, ["--id", a.id], a.n, host_threads(), a.cpu_repeats)
         # (rounds 1-5 timed an x86-64-v3 build: one run of it, for continuity)
@@ -476,7 +550,7 @@ def main():
         "cpu_baseline": cpu,
         "extra": {"nw_cell_updates_per_s": nw_rate, "nw_roofline": nw_roof, "kernel_rooflines": others,
                   "clusters": s0["clusters"], "dominant_family": dominant,
-                  "resident_sequences_per_s": round(a.n / min(res_t), 1),
+                  "resident_sequences_per_s": round(a.n / min(res_t), 1) if res_t else None,  # (--full)
                   "resident_ms_per_run": [round(x * 1e3, 2) for x in res_t],
                   "step_split_ms": {"parse": round(1e3 * sum(s["parse_s"] for s in stats) / a.steps, 2),
                                     "upload_to_partition": round(sum(s["phases_ms"]["total_pipeline"]
@@ -524,6 +598,8 @@ def main():
                               "write_clstr": round(sum(s["write_ms"] for s in d_stats) / nd, 2)},
             "device_ms_per_step": {f: round(v[0] / nd, 3) for f, v in d_tim.items()},
             "comm_ms_per_step": comm_summary(d_stats), "warmup_s": round(d_first, 3)}
+    if a.dump_outputs and keep_src:
+        dump_outputs(a.dump_outputs, fasta, keep_src)
     print(json.dumps(line), flush=True)
     if a.stats_out:
         with open(a.stats_out, "w") as f:

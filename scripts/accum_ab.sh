@@ -23,7 +23,7 @@ PY
 for v in ${VARIANTS:-base}; do
   envs=(); [ "$v" != base ] && envs=(${v//,/ })
   echo "== $v"
-  env "${envs[@]}" timeout -k 10 300 python bench.py --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-config-d \
+  env "${envs[@]}" timeout -k 10 300 python bench.py --full --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-config-d \
     > gpurun_out/ab_$v.log 2>&1 || { echo "bench rc=$?"; tail -n 20 gpurun_out/ab_$v.log; exit 1; }
   summ gpurun_out/ab_$v.log
   env "${envs[@]}" MC_ACCUM_PROFILE=${PROFV:-1} timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-config-d \
