@@ -181,6 +181,32 @@ int mc_classify_pairs(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, uint64_
                       uint8_t *similar, double *combo0, double *sum);
 
 /*
+ * Assign queries to the centres of an existing clustering: all M x C pairs scored on the
+ * device, the best similar centre kept per query.  Centres and queries are point ids of the
+ * loaded sequences (histograms built, a k-mer classifier installed).  Pair (q, j) is a
+ * candidate when sim <= 0, or when (uint64_t)(len_c * sim) <= len_q <= (uint64_t)(len_c / sim)
+ * in double -- the window accumulate gives bvec::get_range (ClusterFactory.cpp:637-654), per
+ * point.  A candidate is scored as feat->compute(query, centre), the candidate-first order of
+ * Trainer::get_close (Trainer.cpp:34-114); decision and combo 0 are bit for bit what
+ * mc_classify_pairs(query, centre) returns.
+ *   best[q]       index j into centre_ids (not the id) of the largest combo 0 among the centres
+ *                 classified similar, ties to the lowest j; MC_ASSIGN_NONE if none is similar
+ *   best_val[q]   that combo 0, or -1.0
+ *   n_similar[q]  how many centres are similar
+ *   stats         (may be NULL, else 3 entries) {candidate pairs after the length gate, pairs
+ *                 whose decision fell back from the short scorer to the full one, device time
+ *                 in us from HIP events}
+ * Any output pointer may be NULL.  M = 0 is MC_OK; C = 0 or an id >= n is MC_ERR_ARG.
+ * MC_ERR_UNSUPPORTED: 32/64-bit histograms, a row that does not fit an LDS tile (k >= 8), an
+ * alignment-mode classifier -- the caller then scores the pairs with mc_classify_pairs.
+ * Environment, read per call: MC_ASSIGN_TILE=<centres per LDS tile>, MC_ASSIGN_FORM=general
+ * (the 16-lanes-per-query kernel also where the lane-per-query one applies).
+ */
+#define MC_ASSIGN_NONE 0xffffffffu
+int mc_assign(mc_ctx *ctx, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
+              double sim, uint32_t *best, double *best_val, uint32_t *n_similar, uint64_t *stats);
+
+/*
  * Batched utility::GlobAlignE(seqA,0,la-1,seqB,0,lb-1,1,-1,2,1).getIdentity() on the loaded
  * sequences (GlobAlignE.cpp:123-305; called by Trainer::align, Trainer.cpp:15-31, and
  * Feature::align, Feature.cpp:221-243).  len/ids may be NULL.

@@ -27,6 +27,8 @@ HEADER = os.path.join(ROOT, "include", "meshclust_amd.h")
 FEAT_ALIGN, FEAT_LD, FEAT_MANHATTAN = 1, 2, 4
 FEAT_INTERSECTION, FEAT_PEARSON, FEAT_KULCZYNSKI2 = 16, 32, 1024
 COMBO_SQUARED, COMBO_SELF = 1, 2
+ASSIGN_NONE = 0xFFFFFFFF
+ERR_ARG, ERR_UNSUPPORTED = 1, 6
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
 
@@ -90,12 +92,14 @@ def gpu_lib():
                      "mc_nw_identity_raw", "mc_set_order", "mc_kill", "mc_cluster_begin", "mc_scan",
                      "mc_mean_shift", "mc_update_iteration", "mc_timers", "mc_classify_values", "mc_mean_shift_select", "mc_accumulate",
                      "mc_scan_part", "mc_scan_commit", "mc_comm_unique_id", "mc_comm_create", "mc_comm_allgather",
-                     "mc_comm_stats", "mc_comm_destroy", "mc_sync"):
+                     "mc_comm_stats", "mc_comm_destroy", "mc_sync", "mc_assign"):
             getattr(lib, name).restype = C.c_int
         lib.mc_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
         lib.mc_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.mc_comm_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         lib.mc_comm_destroy.argtypes = [C.c_void_p, C.c_int]
+        lib.mc_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_double,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _gpu = lib
     return _gpu
 
@@ -122,6 +126,9 @@ def host_lib():
         lib.mcl_run_sharded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_char_p,
                                         C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         lib.mcl_tune_host_heap.restype = C.c_int
+        lib.mcl_assign.restype = C.c_int
+        lib.mcl_assign.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                   C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -134,7 +141,9 @@ def tune_host_heap():
 
 def _check(rc, what):
     if rc != 0:
-        raise MCError("%s failed (%d): %s" % (what, rc, gpu_lib().mc_last_error().decode()))
+        e = MCError("%s failed (%d): %s" % (what, rc, gpu_lib().mc_last_error().decode()))
+        e.code = rc
+        raise e
 
 
 class Engine:
@@ -245,6 +254,21 @@ class Engine:
                "mc_classify_pairs")
         return sim, c0, s
 
+    def assign(self, centres, queries, sim=0.0):
+        """mc_assign: every query scored against every centre (point ids) on the device ->
+        (best centre index or ASSIGN_NONE, its combo 0 or -1.0, similar centres per query,
+        [candidate pairs, fall-backs to the full scorer, device time in us])."""
+        centres = np.ascontiguousarray(centres, np.uint32)
+        queries = np.ascontiguousarray(queries, np.uint32)
+        m = len(queries)
+        best = np.full(m, ASSIGN_NONE, np.uint32)
+        val = np.full(m, -1.0)
+        nsim = np.zeros(m, np.uint32)
+        stats = np.zeros(3, np.uint64)
+        _check(self.lib.mc_assign(self.ctx, _p(centres), len(centres), _p(queries), m, float(sim), _p(best), _p(val),
+                                  _p(nsim), _p(stats)), "mc_assign")
+        return best, val, nsim, stats
+
     def classify_values(self, raw):
         """raw: (m, n_single) precomputed single-feature values -> (similar, combo0, sum)."""
         raw = np.ascontiguousarray(raw, np.float64)
@@ -323,6 +347,24 @@ class Engine:
         out = np.zeros(2 * len(FAMILIES))
         _check(self.lib.mc_timers(self.ctx, _p(out), len(out), 1 if reset else 0), "mc_timers")
         return {f: (out[2 * i], int(out[2 * i + 1])) for i, f in enumerate(FAMILIES)}
+
+
+def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8):
+    """Place the reads of the FASTA file(s) ``reads`` into the clustering saved by
+    ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
+    engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
+    similar centres) and, if given, the unassigned reads as FASTA; returns the stats dict."""
+    import json
+    lib = host_lib()
+    files = [reads] if isinstance(reads, str) else list(reads)
+    arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
+    buf = C.create_string_buffer(1 << 14)
+    rc = lib.mcl_assign(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                        unassigned.encode() if unassigned else None, buf, len(buf))
+    st = json.loads(buf.value.decode() or "{}")
+    if rc != 0 or "error" in st:
+        raise MCError("mcl_assign failed (%d): %s" % (rc, st.get("error", st)))
+    return st
 
 
 class Dataset:

@@ -1,0 +1,376 @@
+// assign.hip -- mc_assign: M queries x C centres -> the best similar centre of every query.
+//
+// Placing new reads into an existing clustering is all-pairs scoring with an argmax per query:
+// pair (q, j) is feat->compute(query q, centre j) -- the query first, as Trainer::get_close
+// scores a candidate against a centre (Trainer.cpp:34-114; scan_kernel, k2.hip) -- gated by the
+// length window accumulate gives get_range (ClusterFactory.cpp:637-654), applied per point.
+//
+//   assign_short_kernel    8-bit rows of at most 16 chunks (k <= 4), the trainer's classifier
+//                          layout, classify_small available: a query per lane, its row in 16
+//                          uint4 registers, a tile of centres in LDS read at the same address by
+//                          every lane (broadcast), v_sad_u8 + v_dot4_u32_u8 per chunk, then
+//                          classify_small, and classify_std on the spot when it is undecided.
+//                          The running (combo 0, index) and the similar count stay in registers:
+//                          no cross-lane reduction, no atomics on the results.
+//   assign_general_kernel  wider 8-bit rows, 16-bit bins or any other k-mer classifier: 16 lanes
+//                          per query (distance_keys_kernel's second form), the centre tile in
+//                          LDS, Acc<T> -> reduce16 -> finish, then classify_std (layout 3 / 4) or
+//                          raw_fast + classify_raw.  The running result of a query lives in its
+//                          output slots between tiles (always the same lane's).
+//
+// LDS tile: entry e = nch row chunks + 3 info chunks, at tile[e * (nch + 3)]:
+//   short    {mag, len, ap | ~0 (PSm not ok), np}, {da, kq = mag - B ap}, {gate lo, gate hi}
+//   general  {mag, sumsq}, {len, gate lo}, {gate hi, -}
+// Every scorer here is one of features.hpp's (classify_small / classify_std / classify_raw),
+// which return the same decision and combo 0 bit for bit, so the result equals what
+// mc_classify_pairs gives for the same pair.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "features.hpp"
+
+namespace mcg {
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int INFO = 3;                     // info chunks per tile entry
+constexpr size_t TILE_BYTES = 60u * 1024;   // two workgroups per CU of 160 KiB, within the 64 KiB default
+constexpr uint32_t NONE = MC_ASSIGN_NONE;
+
+struct AssignArgs {
+  HistView H;
+  const uint32_t *cid;  // centre ids (C)
+  const uint32_t *qid;  // query ids (M)
+  const uint64_t *glo, *ghi;  // per centre: the length gate's bounds
+  uint64_t M;
+  uint32_t C, tile;
+  int gate;
+  uint32_t *best;
+  double *bval;
+  uint32_t *nsim;
+  unsigned long long *stats;  // {candidate pairs, classify_std fall-backs}
+};
+
+__device__ __forceinline__ PInfo pinfo(const HistView &H, uint32_t id) {
+  return PInfo{H.mag[id], H.sumsq[id], H.len[id]};
+}
+__device__ __forceinline__ uint4 pack2(uint64_t a, uint64_t b) {
+  return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+}
+__device__ __forceinline__ uint64_t lo64(const uint4 &v) { return (uint64_t)v.x | ((uint64_t)v.y << 32); }
+__device__ __forceinline__ uint64_t hi64(const uint4 &v) { return (uint64_t)v.z | ((uint64_t)v.w << 32); }
+
+// the rows of centres c0 .. c0 + cn into the tile (every thread of the workgroup)
+__device__ __forceinline__ void load_tile_rows(const AssignArgs &A, uint4 *tl, uint32_t c0, uint32_t cn, int nch) {
+  const uint32_t ent = (uint32_t)nch + INFO;
+  for (uint32_t t = threadIdx.x; t < cn * (uint32_t)nch; t += NT) {
+    const uint32_t cc = t / (uint32_t)nch, ch = t % (uint32_t)nch;
+    tl[cc * ent + ch] = reinterpret_cast<const uint4 *>(A.H.hist + (uint64_t)A.cid[c0 + cc] * A.H.pitch)[ch];
+  }
+}
+
+// -------------------------------------------------------------------- short form
+__global__ __launch_bounds__(NT) void assign_short_kernel(AssignArgs A, DevClassifier C, FastCls F) {
+  extern __shared__ __attribute__((aligned(16))) uint4 tl[];
+  __shared__ SmallK s_sk;
+  const HistView &H = A.H;
+  const int nch = (H.B + 15) / 16;
+  const uint32_t ent = (uint32_t)nch + INFO;
+  if (threadIdx.x == 0) s_sk = make_smallk(C, F);
+  const uint64_t i = (uint64_t)blockIdx.x * NT + threadIdx.x;
+  const bool valid = i < A.M;
+  const uint32_t q = valid ? A.qid[i] : A.qid[0];  // (an idle lane scores query 0 and stores nothing)
+  uint4 mine[16];
+  {
+    const uint4 *row = reinterpret_cast<const uint4 *>(H.hist + (uint64_t)q * H.pitch);
+#pragma unroll
+    for (int c = 0; c < 16; c++) mine[c] = c < nch ? row[c] : make_uint4(0, 0, 0, 0);
+  }
+  PSm ps;
+  uint64_t lenq;
+  {
+    const PInfo pq = pinfo(H, q);
+    ps = psmall(pq, pterms(pq.mag, pq.sumsq, H.B));
+    lenq = pq.len;
+  }
+  const double dap = C.layout == 4 ? mk_div((double)ps.mag, (double)H.B, F.rB) : 0.0;
+  double bv = -1.0;
+  uint32_t bj = NONE, ns = 0, ncand = 0, nfb = 0;
+  for (uint32_t c0 = 0; c0 < A.C; c0 += A.tile) {
+    const uint32_t cn = min(A.tile, A.C - c0);
+    __syncthreads();  // (the previous tile's reads are done)
+    load_tile_rows(A, tl, c0, cn, nch);
+    for (uint32_t t = threadIdx.x; t < cn; t += NT) {
+      const uint32_t id = A.cid[c0 + t];
+      const PInfo pc = pinfo(H, id);
+      const PTerms tc = pterms_mk(pc.mag, pc.sumsq, H.B, F.rB);
+      const PSm pm = psmall(pc, tc);
+      const double kq = (double)((int64_t)pc.mag - (int64_t)H.B * tc.ap);
+      uint4 *info = tl + t * ent + nch;
+      info[0] = make_uint4(pm.mag, pm.len, pm.ok ? pm.ap : ~0u, pm.np);
+      info[1] = pack2(__builtin_bit_cast(uint64_t, tc.da), __builtin_bit_cast(uint64_t, kq));
+      info[2] = pack2(A.glo[c0 + t], A.ghi[c0 + t]);
+    }
+    __syncthreads();
+    for (uint32_t e = 0; e < cn; e++) {
+      const uint4 *ce = tl + e * ent;  // (the same address in every lane: broadcast reads)
+      const uint4 g = ce[nch + 2];
+      const bool pass = valid && (!A.gate || (lo64(g) <= lenq && lenq <= hi64(g)));
+      if (__ballot(pass) == 0) continue;  // (uniform: no lane of this wave passes the gate)
+      Acc<uint8_t> acc;
+#pragma unroll
+      for (int c = 0; c < 16; c++)
+        if (c < nch) acc.add(mine[c], ce[c]);
+      if (pass) {
+        ncand++;
+        const uint4 inf = ce[nch];
+        double cv = -1.0;
+        int d = 0;
+        bool und = true;
+        if (ps.ok && inf.z != ~0u) {
+          const uint4 i1 = ce[nch + 1];
+          const SmallK sk = lds_smallk(&s_sk);
+          const PSm pc{inf.x, inf.y, inf.z, inf.w, true};
+          acc.fold();
+          d = classify_small(sk, acc.sad, acc.dot, ps, pc, __builtin_bit_cast(double, hi64(i1)), dap,
+                             __builtin_bit_cast(double, lo64(i1)), H.B, &cv, &und);
+        }
+        if (und) {  // classify_small undecided or not applicable: classify_std from the same sums
+          nfb++;
+          const uint32_t id = A.cid[c0 + e];
+          const PInfo pq = pinfo(H, q), pc = pinfo(H, id);
+          d = classify_std(C, acc.finish(pq.mag, pc.mag), pq, pterms(pq.mag, pq.sumsq, H.B), pc,
+                           pterms(pc.mag, pc.sumsq, H.B), H.B, &cv);
+        }
+        if (d) {
+          ns++;
+          if (bj == NONE || cv > bv) {  // (ascending j: a tie keeps the lowest index)
+            bv = cv;
+            bj = c0 + e;
+          }
+        }
+      }
+    }
+  }
+  if (valid) {
+    A.best[i] = bj;
+    A.bval[i] = bv;
+    A.nsim[i] = ns;
+  }
+  ncand = wave_sum32_all(ncand);  // (<= 64 * C per wave)
+  nfb = wave_sum32_all(nfb);
+  if ((threadIdx.x & 63) == 0) {
+    if (ncand) atomicAdd(&A.stats[0], (unsigned long long)ncand);
+    if (nfb) atomicAdd(&A.stats[1], (unsigned long long)nfb);
+  }
+}
+
+// -------------------------------------------------------------------- general form
+template <typename T>
+__global__ __launch_bounds__(NT) void assign_general_kernel(AssignArgs A, DevClassifier C) {
+  extern __shared__ __attribute__((aligned(16))) uint4 tl[];
+  const HistView &H = A.H;
+  const int nch = (int)((H.B * (int)sizeof(T) + 15) / 16);
+  const uint32_t ent = (uint32_t)nch + INFO;
+  const int lane = threadIdx.x & 63, group = lane >> 4, lig = lane & 15, wave = wave_id();
+  const int rows_per_block = 16;  // 4 waves x 4 groups
+  const int per = (nch + 15) / 16;
+  // chunks of the query's row kept in registers per lane (16-bit bins: fewer, their element
+  // arithmetic is 64-bit); the rest of a wider row is streamed from global memory
+  constexpr int RCH = sizeof(T) == 1 ? 16 : 4;
+  uint32_t ncand = 0;
+  for (uint32_t c0 = 0; c0 < A.C; c0 += A.tile) {
+    const uint32_t cn = min(A.tile, A.C - c0);
+    __syncthreads();
+    load_tile_rows(A, tl, c0, cn, nch);
+    for (uint32_t t = threadIdx.x; t < cn; t += NT) {
+      const PInfo pc = pinfo(H, A.cid[c0 + t]);
+      uint4 *info = tl + t * ent + nch;
+      info[0] = pack2(pc.mag, pc.sumsq);
+      info[1] = pack2(pc.len, A.glo[c0 + t]);
+      info[2] = pack2(A.ghi[c0 + t], 0);
+    }
+    __syncthreads();
+    for (uint64_t base = (uint64_t)blockIdx.x * rows_per_block; base < A.M; base += (uint64_t)gridDim.x * rows_per_block) {
+      const uint64_t i = base + wave * 4 + group;
+      const bool valid = i < A.M;
+      const uint32_t id = valid ? A.qid[i] : A.qid[0];
+      const uint8_t *row = H.hist + (uint64_t)id * H.pitch;
+      uint4 mine[RCH];  // chunks lig, lig + 16, ..: both loops unrolled, so it stays in registers
+#pragma unroll
+      for (int u = 0; u < RCH; u++) {
+        const int ch = lig + 16 * u;
+        mine[u] = (u < per && ch < nch) ? reinterpret_cast<const uint4 *>(row)[ch] : make_uint4(0, 0, 0, 0);
+      }
+      const PInfo pq = pinfo(H, id);
+      const PTerms tq = pterms(pq.mag, pq.sumsq, H.B);
+      // the query's running result: its output slots between tiles (this lane wrote them)
+      const bool owner = valid && lig == 0;
+      double bv = -1.0;
+      uint32_t bj = NONE, ns = 0;
+      if (owner && c0 > 0) {
+        bv = A.bval[i];
+        bj = A.best[i];
+        ns = A.nsim[i];
+      }
+      for (uint32_t e = 0; e < cn; e++) {
+        const uint4 *ce = tl + e * ent;
+        const uint4 i0 = ce[nch], i1 = ce[nch + 1], i2 = ce[nch + 2];
+        const bool pass = valid && (!A.gate || (hi64(i1) <= pq.len && pq.len <= lo64(i2)));
+        if (__ballot(pass) == 0) continue;  // (uniform)
+        Acc<T> acc;
+#pragma unroll
+        for (int u = 0; u < RCH; u++) {
+          const int ch = lig + 16 * u;
+          if (u < per && ch < nch) acc.add(mine[u], ce[ch]);
+        }
+        for (int ch = lig + 16 * RCH; ch < nch; ch += 16) acc.add(reinterpret_cast<const uint4 *>(row)[ch], ce[ch]);
+        acc.reduce16();
+        if (pass && lig == 0) {
+          ncand++;
+          const PInfo pc{lo64(i0), hi64(i0), lo64(i1)};
+          const PS s = acc.finish(pq.mag, pc.mag);
+          double cv;
+          int d;
+          if (C.layout) {
+            d = classify_std(C, s, pq, tq, pc, pterms(pc.mag, pc.sumsq, H.B), H.B, &cv);
+          } else {
+            double raw[MC_MAX_SINGLE];
+#pragma unroll
+            for (int f = 0; f < MC_MAX_SINGLE; f++) raw[f] = f < C.c.n_single ? raw_fast(C.c.lookup[f], s, pq, pc, H.B) : 0.0;
+            d = classify_raw(C, raw, &cv, nullptr);
+          }
+          if (d) {
+            ns++;
+            if (bj == NONE || cv > bv) {
+              bv = cv;
+              bj = c0 + e;
+            }
+          }
+        }
+      }
+      if (owner) {
+        A.best[i] = bj;
+        A.bval[i] = bv;
+        A.nsim[i] = ns;
+      }
+    }
+  }
+  ncand = wave_sum32_all(ncand);
+  if (lane == 0 && ncand) atomicAdd(&A.stats[0], (unsigned long long)ncand);
+}
+
+}  // namespace
+
+}  // namespace mcg
+
+using namespace mcg;
+
+extern "C" int mc_assign(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
+                         double sim, uint32_t *best, double *best_val, uint32_t *n_similar, uint64_t *stats) {
+  if (!c || c->k == 0 || !c->has_cls) return MC_ERR_STATE;
+  if (c->cls.align) {
+    set_error("mc_assign: an alignment-mode classifier has no k-mer scorer (use mc_nw_identity + mc_classify_values)");
+    return MC_ERR_UNSUPPORTED;
+  }
+  if (c->width != 1 && c->width != 2) {
+    set_error("mc_assign: 32/64-bit histograms are not supported (use mc_classify_pairs)");
+    return MC_ERR_UNSUPPORTED;
+  }
+  if (!centre_ids || C == 0 || (M > 0 && !query_ids)) {
+    set_error("mc_assign: no centres (or no query ids)");
+    return MC_ERR_ARG;
+  }
+  for (uint32_t j = 0; j < C; j++)
+    if (centre_ids[j] >= c->n) {
+      set_error("point id out of range");
+      return MC_ERR_ARG;
+    }
+  for (uint64_t i = 0; i < M; i++)
+    if (query_ids[i] >= c->n) {
+      set_error("point id out of range");
+      return MC_ERR_ARG;
+    }
+  if (stats) stats[0] = stats[1] = stats[2] = 0;
+  if (M == 0) return MC_OK;
+  const HistView H = hist_view(c);
+  const int nch = (int)((H.B * H.width + 15) / 16);
+  const size_t ent_bytes = (size_t)(nch + INFO) * 16;
+  if (ent_bytes > TILE_BYTES) {
+    set_error("mc_assign: a histogram row does not fit an LDS tile (use mc_classify_pairs)");
+    return MC_ERR_UNSUPPORTED;
+  }
+  uint32_t tile = (uint32_t)std::min<size_t>(TILE_BYTES / ent_bytes, C);
+  if (const char *t = getenv("MC_ASSIGN_TILE")) {
+    const long v = atol(t);
+    if (v >= 1) tile = (uint32_t)std::min<long>(v, (long)tile);
+  }
+  const char *form = getenv("MC_ASSIGN_FORM");
+  const bool general = form && !strcmp(form, "general");
+  const bool is_short = !general && c->width == 1 && nch <= 16 && c->cls.layout != 0 && c->fcls.on && c->fcls.mk;
+  MCG_CHECK(hipSetDevice(c->device));
+  // the gate's bounds per centre: accumulate's get_range arguments (ClusterFactory.cpp:650)
+  std::vector<uint64_t> gate(2 * (size_t)C, 0);
+  if (sim > 0)
+    for (uint32_t j = 0; j < C; j++) {
+      const uint64_t len = c->h_seq_off[centre_ids[j] + 1] - c->h_seq_off[centre_ids[j]];
+      gate[j] = (uint64_t)(len * sim);
+      gate[C + j] = (uint64_t)(len / sim);
+    }
+  const size_t res_off = ((size_t)M * 4 + 15) / 16 * 16;  // s_f: best, n_similar, then the two counters
+  if (int rc = ensure(c->s_a, (size_t)C * 4 + 16)) return rc;
+  if (int rc = ensure(c->s_b, (size_t)M * 4 + 16)) return rc;
+  if (int rc = ensure(c->s_c, (size_t)C * 16 + 16)) return rc;
+  if (int rc = ensure(c->s_e, (size_t)M * 8 + 16)) return rc;
+  if (int rc = ensure(c->s_f, 2 * res_off + 64)) return rc;
+  AssignArgs A;
+  A.H = H;
+  A.cid = (const uint32_t *)c->s_a.p;
+  A.qid = (const uint32_t *)c->s_b.p;
+  A.glo = (const uint64_t *)c->s_c.p;
+  A.ghi = A.glo + C;
+  A.M = M;
+  A.C = C;
+  A.tile = tile;
+  A.gate = sim > 0 ? 1 : 0;
+  A.best = (uint32_t *)c->s_f.p;
+  A.nsim = (uint32_t *)((char *)c->s_f.p + res_off);
+  A.stats = (unsigned long long *)((char *)c->s_f.p + 2 * res_off);
+  A.bval = (double *)c->s_e.p;
+  MCG_CHECK(hipMemcpyAsync(c->s_a.p, centre_ids, (size_t)C * 4, hipMemcpyHostToDevice, c->stream));
+  MCG_CHECK(hipMemcpyAsync(c->s_b.p, query_ids, (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
+  MCG_CHECK(hipMemcpyAsync(c->s_c.p, gate.data(), (size_t)C * 16, hipMemcpyHostToDevice, c->stream));
+  MCG_CHECK(hipMemsetAsync(A.stats, 0, 16, c->stream));
+  const size_t lds = (size_t)tile * ent_bytes;
+  MCG_CHECK(hipEventRecord(c->ev0, c->stream));
+  if (is_short) {
+    FastCls F = c->fcls;
+    F.rB = 1.0 / (double)H.B;
+    const unsigned grid = (unsigned)((M + NT - 1) / NT);
+    assign_short_kernel<<<grid, NT, lds, c->stream>>>(A, c->cls, F);
+  } else {
+    const unsigned grid = (unsigned)std::min<uint64_t>((M + 15) / 16, 1024);
+    if (c->width == 1) assign_general_kernel<uint8_t><<<grid, NT, lds, c->stream>>>(A, c->cls);
+    else assign_general_kernel<uint16_t><<<grid, NT, lds, c->stream>>>(A, c->cls);
+  }
+  MCG_CHECK(hipGetLastError());
+  MCG_CHECK(hipEventRecord(c->ev1, c->stream));
+  unsigned long long cnt[2] = {0, 0};
+  if (best) MCG_CHECK(hipMemcpyAsync(best, A.best, (size_t)M * 4, hipMemcpyDeviceToHost, c->stream));
+  if (best_val) MCG_CHECK(hipMemcpyAsync(best_val, A.bval, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+  if (n_similar) MCG_CHECK(hipMemcpyAsync(n_similar, A.nsim, (size_t)M * 4, hipMemcpyDeviceToHost, c->stream));
+  MCG_CHECK(hipMemcpyAsync(cnt, A.stats, 16, hipMemcpyDeviceToHost, c->stream));
+  MCG_CHECK(hipStreamSynchronize(c->stream));
+  float ms = 0;
+  MCG_CHECK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  flush_timers(c);
+  if (stats) {
+    stats[0] = cnt[0];
+    stats[1] = cnt[1];
+    stats[2] = (uint64_t)((double)ms * 1000.0 + 0.5);
+  }
+  return MC_OK;
+}

@@ -1,0 +1,244 @@
+// assign.cpp -- see assign.hpp.
+#include "assign.hpp"
+
+#include <sys/stat.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#ifdef _OPENMP
+#include <omp.h>
+#endif
+
+#include "fasta.hpp"
+#include "model.hpp"
+
+namespace mc {
+
+static const char *kUsage =
+    "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
+    "[--unassigned rest.fa] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n";
+
+AssignOptions parse_assign_options(int argc, char **argv) {
+  AssignOptions o;
+  for (int i = 1; i < argc; i++) {
+    const std::string arg = argv[i];
+    const bool has = i + 1 < argc;
+    if (arg == "--model" && has) o.model = argv[++i];
+    else if (arg == "--centres" && has) o.centres = argv[++i];
+    else if ((arg == "-o" || arg == "--output") && has) o.output = argv[++i];
+    else if (arg == "--unassigned" && has) o.unassigned = argv[++i];
+    else if (arg == "--stats-json" && has) o.stats_json = argv[++i];
+    else if (arg == "--device" && has) o.device = atoi(argv[++i]);
+    else if ((arg == "-t" || arg == "--threads") && has) {
+      o.threads = atoi(argv[++i]);
+      if (o.threads <= 0) throw Error("Number of threads must be greater than 0.", 1);
+    } else if (arg == "--quiet") o.quiet = true;
+    else {
+      struct stat st;
+      if (stat(argv[i], &st) == 0 && S_ISREG(st.st_mode)) o.reads.push_back(argv[i]);
+      else throw Error(std::string("unknown option or missing file: ") + argv[i] + "\n" + kUsage, 1);
+    }
+  }
+  if (o.model.empty() || o.centres.empty() || o.reads.empty())
+    throw Error(std::string("--model, --centres and at least one reads file are required\n") + kUsage, 1);
+  return o;
+}
+
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The same job through mc_classify_pairs: the candidate pairs of the length gate in batches,
+// the argmax on the host (largest combo 0 among the similar centres, lowest index on ties).
+static void assign_by_pairs(mc_ctx *ctx, const Dataset &ds, uint32_t C, uint64_t M, double sim,
+                            std::vector<uint32_t> &best, std::vector<double> &val, std::vector<uint32_t> &nsim,
+                            uint64_t *candidates) {
+  std::vector<uint64_t> lo(C, 0), hi(C, ~0ull);
+  if (sim > 0)
+    for (uint32_t j = 0; j < C; j++) {
+      lo[j] = (uint64_t)(ds.lengths[j] * sim);
+      hi[j] = (uint64_t)(ds.lengths[j] / sim);
+    }
+  const size_t batch = 1u << 22;
+  std::vector<uint32_t> a, b;
+  std::vector<uint8_t> d;
+  std::vector<double> c0;
+  a.reserve(batch + C);
+  b.reserve(batch + C);
+  auto flush = [&]() {
+    if (a.empty()) return;
+    d.resize(a.size());
+    c0.resize(a.size());
+    check(mc_classify_pairs(ctx, a.data(), b.data(), a.size(), d.data(), c0.data(), nullptr), "mc_classify_pairs");
+    for (size_t p = 0; p < a.size(); p++) {  // (pairs are query-major, centres ascending)
+      if (!d[p]) continue;
+      const uint64_t q = a[p] - C;
+      nsim[q]++;
+      if (best[q] == MC_ASSIGN_NONE || c0[p] > val[q]) {
+        best[q] = b[p];
+        val[q] = c0[p];
+      }
+    }
+    *candidates += a.size();
+    a.clear();
+    b.clear();
+  };
+  for (uint64_t q = 0; q < M; q++) {
+    const uint64_t len = ds.lengths[C + q];
+    for (uint32_t j = 0; j < C; j++)
+      if (lo[j] <= len && len <= hi[j]) {
+        a.push_back((uint32_t)(C + q));
+        b.push_back(j);
+      }
+    if (a.size() >= batch) flush();
+  }
+  flush();
+}
+
+AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
+  AssignResult r;
+  struct Own {  // a context of the tool's own, opened only once the inputs are accepted
+    mc_ctx *c = nullptr;
+    ~Own() {
+      if (c) mc_ctx_destroy(c);
+    }
+  } own;
+  int threads = opt.threads;
+#ifdef _OPENMP
+  if (threads <= 0) threads = omp_get_max_threads();
+#else
+  threads = 1;
+#endif
+  const Model model = read_model(opt.model);
+  if (model.align)
+    throw Error("meshclust-assign: " + opt.model +
+                    " is an alignment-mode model (--align or --id below 0.6); only k-mer classifiers can be assigned against",
+                2);
+  auto t0 = std::chrono::steady_clock::now();
+  std::vector<std::string> files{opt.centres};
+  files.insert(files.end(), opt.reads.begin(), opt.reads.end());
+  Dataset ds;
+  parse_fasta_files(files, ds, threads);  // centres first: their ids are 0 .. C-1
+  r.parse_ms = ms_since(t0);
+  const uint64_t C = ds.file_count.empty() ? 0 : ds.file_count[0];
+  if (C != model.centres)
+    throw Error("meshclust-assign: " + opt.centres + " holds " + std::to_string(C) + " records, the model was saved with " +
+                    std::to_string(model.centres) + " centres",
+                2);
+  if (C == 0) throw Error("meshclust-assign: no centres", 2);
+  const uint64_t M = ds.size() - C;
+  r.reads = M;
+  r.centres = C;
+  r.k = model.k;
+  if (!ctx) {
+    check(mc_ctx_create(opt.device, &own.c), "mc_ctx_create");
+    ctx = own.c;
+  }
+  t0 = std::chrono::steady_clock::now();
+  check(mc_load_packed(ctx, ds.packed.data(), ds.pk_off.data(), ds.seq_off.data(), ds.size(), ds.exc_pos.data(),
+                       ds.exc_val.data(), ds.exc_pos.size(), ds.seg.data(), ds.seg_off.data()),
+        "mc_load_packed");
+  r.upload_ms = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  uint64_t largest = 0;
+  check(mc_kmer_max(ctx, model.k, &largest), "mc_kmer_max");
+  int width = largest <= 0xff ? 1 : largest <= 0xffff ? 2 : largest <= 0xffffffffull ? 4 : 8;  // as run_pipeline
+  if (const char *fw = getenv("MC_FORCE_WIDTH")) width = std::max(width, atoi(fw));
+  r.width = width;
+  check(mc_kmer_build(ctx, model.k, width), "mc_kmer_build");
+  check(mc_set_classifier(ctx, &model.cls), "mc_set_classifier");
+  r.kmer_ms = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  std::vector<uint32_t> best(M, MC_ASSIGN_NONE), nsim(M, 0);
+  std::vector<double> val(M, -1.0);
+  bool by_pairs = getenv("MC_ASSIGN_PAIRS") && atoi(getenv("MC_ASSIGN_PAIRS")) != 0;
+  if (!by_pairs) {
+    std::vector<uint32_t> cid(C), qid(M);
+    for (uint64_t j = 0; j < C; j++) cid[j] = (uint32_t)j;
+    for (uint64_t q = 0; q < M; q++) qid[q] = (uint32_t)(C + q);
+    uint64_t st[3] = {0, 0, 0};
+    const int rc = mc_assign(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, best.data(), val.data(), nsim.data(), st);
+    if (rc == MC_ERR_UNSUPPORTED) {  // wide bins or rows: the pair list does the same job
+      if (!opt.quiet) fprintf(stderr, "meshclust-assign: %s; scoring with mc_classify_pairs\n", mc_last_error());
+      by_pairs = true;
+    } else {
+      check(rc, "mc_assign");
+      r.candidates = st[0];
+      r.fallbacks = st[1];
+      r.device_us = st[2];
+    }
+  }
+  if (by_pairs) assign_by_pairs(ctx, ds, (uint32_t)C, M, model.id, best, val, nsim, &r.candidates);
+  r.path = by_pairs ? "pairs" : "device";
+  r.assign_ms = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  // one line per read, in input order: read header, centre header or *, cluster index or -1,
+  // combo 0, similar centres (headers without their '>')
+  std::string out;
+  std::vector<uint32_t> rest;
+  char num[64];
+  for (uint64_t q = 0; q < M; q++) {
+    const bool has = best[q] != MC_ASSIGN_NONE;
+    out.append(ds.headers[C + q].substr(1));
+    out += '\t';
+    if (has) out.append(ds.headers[best[q]].substr(1));
+    else out += '*';
+    snprintf(num, sizeof num, "\t%d\t%.17g\t%u\n", has ? (int)best[q] : -1, val[q], nsim[q]);
+    out += num;
+    if (has) r.assigned++;
+    else rest.push_back((uint32_t)(C + q));
+  }
+  FILE *f = fopen(opt.output.c_str(), "w");
+  if (!f) throw Error("cannot write " + opt.output + ": " + strerror(errno), 1);
+  const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+  if (fclose(f) != 0 || !ok) throw Error("cannot write " + opt.output, 1);
+  if (!opt.unassigned.empty()) write_fasta(opt.unassigned, ds, rest.data(), rest.size());
+  r.write_ms = ms_since(t0);
+  return r;
+}
+
+std::string assign_stats_json(const AssignResult &r) {
+  char b[768];
+  snprintf(b, sizeof b,
+           "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, \"k\": %d, \"width\": %d, "
+           "\"path\": \"%s\", \"candidate_pairs\": %llu, \"fallback_pairs\": %llu, \"device_us\": %llu, "
+           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, \"write\": %.3f}}",
+           (unsigned long long)r.reads, (unsigned long long)r.centres, (unsigned long long)r.assigned,
+           (unsigned long long)(r.reads - r.assigned), r.k, r.width, r.path.c_str(), (unsigned long long)r.candidates,
+           (unsigned long long)r.fallbacks, (unsigned long long)r.device_us, r.parse_ms, r.upload_ms, r.kmer_ms,
+           r.assign_ms, r.write_ms);
+  return b;
+}
+
+int assign_main(int argc, char **argv) {
+  try {
+    const AssignOptions opt = parse_assign_options(argc, argv);
+#ifdef _OPENMP
+    if (opt.threads > 0) omp_set_num_threads(opt.threads);
+#endif
+    const AssignResult r = run_assign(nullptr, opt);
+    if (!opt.quiet)
+      printf("%llu reads, %llu centres: %llu assigned, %llu unassigned (%s)\n", (unsigned long long)r.reads,
+             (unsigned long long)r.centres, (unsigned long long)r.assigned, (unsigned long long)(r.reads - r.assigned),
+             r.path.c_str());
+    if (!opt.stats_json.empty()) {
+      if (FILE *f = fopen(opt.stats_json.c_str(), "w")) {
+        fprintf(f, "%s\n", assign_stats_json(r).c_str());
+        fclose(f);
+      }
+    }
+    return 0;
+  } catch (const Error &e) {
+    fprintf(stderr, "%s\n", e.what());
+    return e.code ? e.code : 1;
+  } catch (const std::exception &e) {
+    fprintf(stderr, "meshclust-assign: %s\n", e.what());
+    return 1;
+  }
+}
+
+}  // namespace mc

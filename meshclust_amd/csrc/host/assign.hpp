@@ -1,0 +1,37 @@
+// assign.hpp -- bin/meshclust-assign: place reads into an existing clustering (the model and
+// centres files bin/meshclust saves, model.hpp) with mc_assign on the GPU.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+
+namespace mc {
+
+struct AssignOptions {
+  std::string model, centres, output = "assign.tsv", unassigned, stats_json;
+  std::vector<std::string> reads;  // in the order given
+  int device = 0;
+  int threads = 0;  // 0 = OpenMP default
+  bool quiet = false;
+};
+
+struct AssignResult {
+  uint64_t reads = 0, centres = 0, assigned = 0;
+  uint64_t candidates = 0;  // pairs after the length gate
+  uint64_t fallbacks = 0;   // mc_assign: pairs decided by the full scorer
+  uint64_t device_us = 0;   // mc_assign: kernel time from HIP events
+  int k = 0, width = 0;
+  std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
+  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, write_ms = 0;
+};
+
+// Throws mc::Error (bad options: code 1 with the usage text in what()).
+AssignOptions parse_assign_options(int argc, char **argv);
+// The whole job; writes the TSV (and the unassigned FASTA).  ctx NULL: a context on opt.device is
+// opened once the model and the centres file are accepted, and closed at the end.
+AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
+std::string assign_stats_json(const AssignResult &r);
+int assign_main(int argc, char **argv);
+
+}  // namespace mc

@@ -84,6 +84,7 @@ static int run_common(void *dsv, mc_ctx *ctx, int argc, char **argv, int upload,
     mc::RunResult rr = mc::run_pipeline(*ds, ctx, opt, upload != 0, comm);
     const auto t1 = std::chrono::steady_clock::now();
     if (clstr_path) mc::write_clstr(clstr_path, *ds, rr.part, opt.threads > 0 ? opt.threads : 1);
+    if (!comm || comm->rank == 0) mc::save_model_files(opt, *ds, rr);
     const double write_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     std::string js = mc::stats_json(rr, 0, write_ms);
     if (stats && cap > 0) snprintf(stats, cap, "%s", js.c_str());

@@ -1,0 +1,55 @@
+// capi_assign.cpp -- libmeshclust.so's C entries for read assignment (assign.hpp) and the
+// FASTA writer of model.hpp (used by the Python package and the tests).
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "assign.hpp"
+#include "fasta.hpp"
+#include "model.hpp"
+
+extern "C" {
+
+// Assign the reads of reads[0..nreads) to the centres of a saved clustering on an open context
+// (assign.hpp run_assign): writes the TSV to `tsv` and, if `unassigned` is non-NULL, the
+// unassigned reads as FASTA.  The JSON summary goes to stats (cap bytes).  Returns 0 or an
+// error code with {"error": ...} in stats; an error never ends the calling process.
+int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
+               const char *tsv, const char *unassigned, char *stats, int cap) {
+  try {
+    mc::AssignOptions opt;
+    opt.model = model ? model : "";
+    opt.centres = centres ? centres : "";
+    for (int i = 0; i < nreads; i++) opt.reads.push_back(reads[i]);
+    opt.threads = threads;
+    if (tsv) opt.output = tsv;
+    if (unassigned) opt.unassigned = unassigned;
+    opt.quiet = true;
+    if (opt.model.empty() || opt.centres.empty() || opt.reads.empty()) throw mc::Error("mcl_assign: model, centres and reads are required", 1);
+    const mc::AssignResult r = mc::run_assign(ctx, opt);
+    if (stats && cap > 0) snprintf(stats, cap, "%s", mc::assign_stats_json(r).c_str());
+    return 0;
+  } catch (const std::exception &e) {
+    std::string m;
+    for (const char *c = e.what(); *c; c++) {
+      if (*c == '"' || *c == '\\') m += '\\';
+      m += (unsigned char)*c < 0x20 ? ' ' : *c;
+    }
+    if (stats && cap > 0) snprintf(stats, cap, "{\"error\": \"%s\"}", m.c_str());
+    const mc::Error *me = dynamic_cast<const mc::Error *>(&e);
+    return me && me->code ? me->code : 1;
+  }
+}
+
+// Records ids[0..n) of a parsed dataset (mcl_parse) as FASTA: header lines unchanged, each
+// sequence upper-cased on one line.  Returns 0, or 1 with the message in err.
+int mcl_write_fasta(void *dsv, const uint32_t *ids, uint64_t n, const char *path, char *err, int errcap) {
+  try {
+    mc::write_fasta(path, *(const mc::Dataset *)dsv, ids, n);
+    return 0;
+  } catch (const std::exception &e) {
+    if (err && errcap > 0) snprintf(err, errcap, "%s", e.what());
+    return 1;
+  }
+}
+}

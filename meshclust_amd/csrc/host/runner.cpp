@@ -1,6 +1,8 @@
 // runner.cpp -- see runner.hpp.
 #include "runner.hpp"
 
+#include "model.hpp"
+
 #include <libgen.h>
 #include <malloc.h>
 #include <sys/stat.h>
@@ -30,7 +32,7 @@ namespace mc {
 static void usage(const char *prog) {
   printf("Usage: %s *.fasta [--id 0.90] [--kmer 3] [--delta 5] [--output output.clstr] [--iterations 20] "
          "[--align] [--sample 3000] [--pivot 40] [--threads TMAX] [--device GPU] [--devices GPU,GPU,..] "
-         "[--stats-json FILE]\n",
+         "[--stats-json FILE] [--save-model FILE] [--save-centres FILE]\n",
          prog);
   printf("MI355X-native MeShClust (meshclust_amd, C-ABI v%d)\n", MC_ABI_VERSION);
 }
@@ -98,6 +100,10 @@ Options parse_options(int argc, char **argv, bool require_files) {
       }
     } else if (arg == "--stats-json" && i + 1 < argc) {
       o.stats_json = argv[++i];
+    } else if (arg == "--save-model" && i + 1 < argc) {
+      o.save_model = argv[++i];
+    } else if (arg == "--save-centres" && i + 1 < argc) {
+      o.save_centres = argv[++i];
     } else if (arg == "--quiet") {
       o.quiet = true;
     } else {
@@ -334,6 +340,9 @@ RunResult run_pipeline(const Dataset &ds, mc_ctx *ctx, Options opt, bool upload,
   if (bvec_err) std::rethrow_exception(bvec_err);
   mc_classifier cls = tr.classifier();
   check(mc_set_classifier(ctx, &cls), "mc_set_classifier");
+  rr.cls = cls;
+  rr.similarity = opt.similarity;
+  rr.align = opt.align;
   ClusterConfig cc;
   cc.sim = opt.similarity;
   cc.iterations = opt.iterations;
@@ -375,6 +384,23 @@ std::string stats_json(const RunResult &rr, double parse_ms, double write_ms) {
   }
   o += "}}";
   return o;
+}
+
+void save_model_files(const Options &opt, const Dataset &ds, const RunResult &rr) {
+  if (!opt.save_model.empty()) {
+    Model m;
+    m.k = rr.k;
+    m.id = rr.similarity;
+    m.align = rr.align ? 1 : 0;
+    m.cls = rr.cls;
+    m.centres = rr.part.size();
+    write_model(opt.save_model, m);
+  }
+  if (!opt.save_centres.empty()) {
+    std::vector<uint32_t> ids;
+    for (const Center &c : rr.part) ids.push_back(c.centre);
+    write_fasta(opt.save_centres, ds, ids.data(), ids.size());
+  }
 }
 
 static void write_stats(const std::string &path, const RunResult &rr, double parse_ms, double write_ms) {
@@ -527,6 +553,7 @@ int meshclust_main(int argc, char **argv) {
     auto t1 = std::chrono::steady_clock::now();
     if (!opt.quiet) printf("Printing output\n");
     write_clstr(opt.output, ds, rr.part, threads);
+    save_model_files(opt, ds, rr);
     double write_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     if (!opt.stats_json.empty()) write_stats(opt.stats_json, rr, parse_ms, write_ms);
     mc_ctx_destroy(ctx);

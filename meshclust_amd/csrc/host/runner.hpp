@@ -28,6 +28,8 @@ struct Options {
   std::vector<int> devices;  // --devices 0,1,..: one clustering shared by these GPUs (RCCL)
   bool quiet = false;
   std::string stats_json;  // per-phase timings + work counts
+  std::string save_model;    // --save-model FILE: k, id, the trained classifier (model.hpp)
+  std::string save_centres;  // --save-centres FILE: the final centres as FASTA, cluster order
 };
 
 // Parses argv like the reference; bad input throws mc::Error (OptionError in runner.cpp)
@@ -42,7 +44,15 @@ struct RunResult {
   int width = 1;
   uint64_t largest = 0;
   size_t n = 0;
+  // what read assignment needs beside the centres (model.hpp): the trained classifier and the
+  // options as the pipeline resolved them
+  mc_classifier cls{};
+  double similarity = 0;
+  bool align = false;
 };
+
+// --save-model / --save-centres of a finished run (where the .clstr is written; rank 0 only).
+void save_model_files(const Options &opt, const Dataset &ds, const RunResult &rr);
 
 // Full pipeline on an already parsed dataset and an open context (bench.py reuses both).
 bool tune_host_heap();  // process-global malloc settings (runner.cpp); true when applied

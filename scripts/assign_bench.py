@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""A/B of read assignment: mc_assign against the mc_classify_pairs pair list.
+
+Clusters the seeded synthetic workload of bench.py (config B: 100k x 1 kb, --id 0.90; --workload D:
+1M x 1 kb), then assigns the same reads to the final centres two ways, alternating in one process
+after a warm-up:
+
+  device  one mc_assign call (stats[2]: kernel time from HIP events; a host clock around the
+          synchronised call beside it)
+  pairs   what a caller had to do before mc_assign: the candidate pairs of the length gate in
+          batches through mc_classify_pairs, the argmax in numpy
+
+Both results are compared for equality first.  Prints one JSON line: both times, their ratio,
+candidate pairs per second, bytes and operations per pair from the shape, and the kernel's share
+of its bound (which bound is named in the line).
+
+Under rocprofv3 set MC_ACCUM_PLAIN_LAUNCH=1, as scripts/prof_round.sh does: the clustering's
+cooperative launch otherwise faults the profiler's exit handler, after the
+profile is written.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench  # noqa: E402  (the workload table and the FASTA cache)
+import meshclust_amd as M  # noqa: E402
+
+SIMDS, CLOCK_HZ = 256 * 4, 2.4e9  # MI355X: 256 CUs x 4 SIMDs, ~2.4 GHz
+
+
+def pairs_pass(eng, centres, queries, lens, sim, batch):
+    """The baseline: gate on the host, mc_classify_pairs per batch, argmax on the host.
+    Returns (best, val, nsim, candidate pairs, seconds inside mc_classify_pairs)."""
+    C_ = len(centres)
+    lc = lens[centres].astype(np.float64)
+    lo = (lc * sim).astype(np.uint64)
+    hi = (lc / sim).astype(np.uint64)
+    best = np.full(len(queries), M.ASSIGN_NONE, np.uint32)
+    val = np.full(len(queries), -1.0)
+    nsim = np.zeros(len(queries), np.uint32)
+    per = max(1, batch // C_)
+    cand, t_call = 0, 0.0
+    for q0 in range(0, len(queries), per):
+        q = queries[q0:q0 + per]
+        lq = lens[q]
+        gate = (lo[None, :] <= lq[:, None]) & (lq[:, None] <= hi[None, :])
+        qi, cj = np.nonzero(gate)
+        t0 = time.perf_counter()
+        d, c0, _ = eng.classify_pairs(q[qi], centres[cj])
+        t_call += time.perf_counter() - t0
+        cand += len(qi)
+        m = np.full(gate.shape, -np.inf)
+        m[qi[d != 0], cj[d != 0]] = c0[d != 0]
+        n = np.zeros(gate.shape, np.uint32)
+        n[qi, cj] = d
+        ns = n.sum(axis=1)
+        b = m.argmax(axis=1)
+        has = ns > 0
+        best[q0:q0 + len(q)] = np.where(has, b, M.ASSIGN_NONE)
+        val[q0:q0 + len(q)] = np.where(has, m[np.arange(len(q)), b], -1.0)
+        nsim[q0:q0 + len(q)] = ns
+    return best, val, nsim, cand, t_call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", choices=sorted(bench.WORKLOADS), default="B")
+    ap.add_argument("--rounds", type=int, default=3, help="timed device / pairs alternations")
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--pairs-rounds", type=int, default=None, help="timed pair-list passes (default: --rounds)")
+    ap.add_argument("--pairs-queries", type=int, default=0,
+                    help="run the pair list on the first N reads only (0: all); its times are then for those "
+                         "reads, and the ratios are per candidate pair (config D: the whole pair list takes minutes)")
+    ap.add_argument("--batch", type=int, default=1 << 22, help="pairs per mc_classify_pairs call")
+    ap.add_argument("--id", type=float, default=0.90)
+    a = ap.parse_args()
+    n, templates, seed = bench.WORKLOADS[a.workload]
+    fasta = bench.ensure_fasta(n, 1000, templates, 0.03, seed)
+    tmp = tempfile.mkdtemp(prefix="mc_assign_bench")
+    model, cen = os.path.join(tmp, "model.txt"), os.path.join(tmp, "centres.fa")
+    ds = M.Dataset([fasta], threads=16)
+    eng = M.Engine(0)
+    st = ds.run(eng, ["--id", str(a.id), "--save-model", model, "--save-centres", cen])
+    # the context still holds the reads, their histograms and the trained classifier
+    ids = {ds.lib.mcl_header(ds.h, i): i for i in range(ds.n)}
+    centres = np.array([ids[ln.rstrip(b"\n")] for ln in open(cen, "rb") if ln.startswith(b">")], np.uint32)
+    queries = np.arange(ds.n, dtype=np.uint32)
+    npq = a.pairs_queries if 0 < a.pairs_queries < ds.n else ds.n
+    seq_off = np.zeros(ds.n + 1, np.uint64)
+    ptr = [M.C.c_void_p() for _ in range(4)]
+    ds.lib.mcl_view(ds.h, *[M.C.byref(p) for p in ptr])
+    seq_off[:] = np.ctypeslib.as_array(M.C.cast(ptr[1], M.C.POINTER(M.C.c_uint64)), shape=(ds.n + 1,))
+    lens = np.diff(seq_off).astype(np.uint64)
+    k, width = st["k"], st["width"]
+    B = 4 ** k
+    nch = (B * width + 15) // 16
+    dev_us, dev_wall, pair_call, pair_dev_ms = [], [], [], []
+    ref = None
+    prounds = a.rounds if a.pairs_rounds is None else a.pairs_rounds
+    for r in range(a.warmup + a.rounds):
+        t0 = time.perf_counter()
+        best, val, nsim, stats = eng.assign(centres, queries, a.id)
+        wall = time.perf_counter() - t0
+        if r == 0 or r - a.warmup < prounds:
+            eng.timers(reset=True)
+            pb, pv, pn, pcand, t_call = pairs_pass(eng, centres, queries[:npq], lens, a.id, a.batch)
+            pdev = eng.timers()["pairs"][0]
+            assert np.array_equal(best[:npq], pb) and np.array_equal(val[:npq], pv) and np.array_equal(nsim[:npq], pn), \
+                "outputs differ"
+            assert npq < ds.n or int(stats[0]) == pcand, (int(stats[0]), pcand)
+            if r >= a.warmup:
+                pair_call.append(t_call)
+                pair_dev_ms.append(pdev)
+        if ref is None:
+            ref = (best.copy(), val.copy(), nsim.copy())
+        assert all(np.array_equal(x, y) for x, y in zip(ref, (best, val, nsim))), "mc_assign is not repeatable"
+        if r >= a.warmup:
+            dev_us.append(int(stats[2]))
+            dev_wall.append(wall)
+    cand = int(stats[0])
+    d_us = float(np.median(dev_us))
+    p_dev_ms = float(np.median(pair_dev_ms))
+    p_call_s = float(np.median(pair_call))
+    short = width == 1 and nch <= 16
+    # per pair, from the shape: every chunk is 4 v_sad_u8 + 4 v_dot4_u32_u8 (8-bit rows); the
+    # centre's row comes from LDS (nch + 3 broadcast 16-byte reads), the query's row from registers;
+    # HBM / L2 traffic per pair: the query's row and results once per query, the centre tile once
+    # per workgroup of 256 queries
+    int_ops = 8 * nch if width == 1 else 0
+    lds_bytes = 16 * (nch + 3)
+    mem_bytes = (nch * 16 + 40) / max(1, len(centres)) + (nch + 3) * 16 / 256.0
+    floor_pairs_s = SIMDS * 64 * CLOCK_HZ / (2.0 * int_ops) if int_ops else None
+    line = {
+        "workload": "config %s: %d reads x 1 kb assigned to the %d centres of their own clustering (--id %s, k %d, %d-bit)" % (
+            a.workload, ds.n, len(centres), a.id, k, 8 * width),
+        "form": "short" if short and not os.environ.get("MC_ASSIGN_FORM") else "general",
+        "candidate_pairs": cand,
+        "fallback_pairs": int(stats[1]),
+        "assigned": int((best != M.ASSIGN_NONE).sum()),
+        "mc_assign_device_us": d_us,
+        "mc_assign_device_us_all": dev_us,
+        "mc_assign_call_wall_ms": round(1e3 * float(np.median(dev_wall)), 3),
+        "pairs_kernel_device_ms": round(p_dev_ms, 3),
+        "pairs_calls_wall_ms": round(1e3 * p_call_s, 3),
+        "pairs_reads": npq,
+        "pairs_candidate_pairs": pcand,
+        "ratio_device_time": round((p_dev_ms * 1e3 / pcand) / (d_us / cand), 2),
+        "ratio_call_time": round((p_call_s / pcand) / (float(np.median(dev_wall)) / cand), 2),
+        "mc_assign_pairs_per_s": round(cand / (d_us * 1e-6), 1),
+        "per_pair": {"packed_int_valu_ops": int_ops, "lds_bytes": lds_bytes, "hbm_l2_bytes": round(mem_bytes, 3),
+                     "pair_list_hbm_l2_bytes": 2 * nch * 16 + 8 + 17},
+        "bound": "VALU issue: the %d packed-integer instructions per pair alone, 2 cycles each per wave64 on a 32-wide SIMD, %d SIMDs at %.1f GHz"
+                 % (int_ops, SIMDS, CLOCK_HZ / 1e9),
+        "bound_pairs_per_s": floor_pairs_s,
+        "share_of_bound": round(cand / (d_us * 1e-6) / floor_pairs_s, 4) if floor_pairs_s else None,
+        "outputs_equal": True,
+    }
+    print(json.dumps(line))
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
