@@ -207,6 +207,46 @@ int mc_assign(mc_ctx *ctx, const uint32_t *centre_ids, uint32_t C, const uint32_
               double sim, uint32_t *best, double *best_val, uint32_t *n_similar, uint64_t *stats);
 
 /*
+ * The histogram rows of the other strand.  With the k-mer index written first base most
+ * significant (A 0, C 1, G 2, T 3), the reverse complement of k-mer i is rc(i): the k base-4
+ * digits of i reversed, each digit d replaced by 3 - d.  rows[r][i] = hist[ids[r]][rc(i)] for the
+ * m points ids, m * 4^k bins of the histograms' width, packed.  For a record whose segments are
+ * all at least k long (every record of the FASTA parser: its segments are at least 20 bases)
+ * this is exactly the histogram of the reverse-complemented record with its segments mirrored,
+ * pseudocounts included; magnitude, sum of squares and length are those of the point itself.
+ * THE MINUS STRAND IS DEFINED AS THIS PERMUTED ROW.  A caller of mc_load_sequences can hand in a
+ * segment shorter than k; such a segment is hashed at its first position only, which is not
+ * mirror-symmetric, so there the permuted row is not the histogram of the mirrored record.
+ * MC_ERR_UNSUPPORTED: 32/64-bit histograms, a row that does not fit an LDS tile (k >= 8).
+ */
+int mc_revcomp_rows(mc_ctx *ctx, const uint32_t *ids, uint64_t m, void *rows /* m * 4^k * width */);
+
+/*
+ * mc_assign on either strand of the queries.  Every scorer input is a bin-wise sum and rc is an
+ * involution, so score(rc(query), centre) == score(query, rc(centre)) bit for bit: the C centre
+ * rows are permuted once per call (mc_revcomp_rows' kernel), not the M query rows.
+ *   strands == MC_STRAND_PLUS    exactly mc_assign; strand[q] = 0
+ *   strands == MC_STRAND_MINUS   what mc_assign returns for the reverse-complemented queries
+ *                                (minus strand as defined above); strand[q] = 1
+ *   strands == both (3)          per query the plus result (j+, v+, n+) and the minus result
+ *                                (j-, v-, n-), each by mc_assign's own rule (largest combo 0, ties
+ *                                to the lowest j).  Minus wins only if j- != MC_ASSIGN_NONE and
+ *                                (j+ == MC_ASSIGN_NONE or v- > v+); a tie goes to plus.
+ *                                strand[q] = 1 where minus wins, else 0 (0 when unassigned);
+ *                                n_similar[q] = n+ + n-.
+ * The length gate does not depend on the strand.  stats[0] stays the (query, centre) pairs after
+ * the gate, stats[1] counts fall-backs per scored (pair, strand), stats[2] is device time
+ * including the permutation kernel.  With both strands a tile entry holds two rows, so rows must
+ * fit twice (k <= 6 at 16 bits, k <= 7 at 8 bits) and MC_ASSIGN_TILE's default roughly halves.
+ * strands outside 1..3 is MC_ERR_ARG; otherwise errors are mc_assign's.
+ */
+#define MC_STRAND_PLUS 1
+#define MC_STRAND_MINUS 2
+int mc_assign_strands(mc_ctx *ctx, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
+                      double sim, int strands /* 1, 2 or 3 */, uint32_t *best, double *best_val,
+                      uint8_t *strand /* 0 plus, 1 minus; 0 when unassigned */, uint32_t *n_similar, uint64_t *stats);
+
+/*
  * Batched utility::GlobAlignE(seqA,0,la-1,seqB,0,lb-1,1,-1,2,1).getIdentity() on the loaded
  * sequences (GlobAlignE.cpp:123-305; called by Trainer::align, Trainer.cpp:15-31, and
  * Feature::align, Feature.cpp:221-243).  len/ids may be NULL.

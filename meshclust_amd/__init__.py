@@ -28,6 +28,7 @@ FEAT_ALIGN, FEAT_LD, FEAT_MANHATTAN = 1, 2, 4
 FEAT_INTERSECTION, FEAT_PEARSON, FEAT_KULCZYNSKI2 = 16, 32, 1024
 COMBO_SQUARED, COMBO_SELF = 1, 2
 ASSIGN_NONE = 0xFFFFFFFF
+MC_STRAND_PLUS, MC_STRAND_MINUS = 1, 2
 ERR_ARG, ERR_UNSUPPORTED = 1, 6
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
@@ -92,7 +93,8 @@ def gpu_lib():
                      "mc_nw_identity_raw", "mc_set_order", "mc_kill", "mc_cluster_begin", "mc_scan",
                      "mc_mean_shift", "mc_update_iteration", "mc_timers", "mc_classify_values", "mc_mean_shift_select", "mc_accumulate",
                      "mc_scan_part", "mc_scan_commit", "mc_comm_unique_id", "mc_comm_create", "mc_comm_allgather",
-                     "mc_comm_stats", "mc_comm_destroy", "mc_sync", "mc_assign"):
+                     "mc_comm_stats", "mc_comm_destroy", "mc_sync", "mc_assign", "mc_assign_strands",
+                     "mc_revcomp_rows"):
             getattr(lib, name).restype = C.c_int
         lib.mc_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
         lib.mc_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -100,6 +102,9 @@ def gpu_lib():
         lib.mc_comm_destroy.argtypes = [C.c_void_p, C.c_int]
         lib.mc_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_double,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mc_assign_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_double, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mc_revcomp_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         _gpu = lib
     return _gpu
 
@@ -129,6 +134,9 @@ def host_lib():
         lib.mcl_assign.restype = C.c_int
         lib.mcl_assign.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                    C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+        lib.mcl_assign_strands.restype = C.c_int
+        lib.mcl_assign_strands.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                           C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -269,6 +277,31 @@ class Engine:
                                   _p(nsim), _p(stats)), "mc_assign")
         return best, val, nsim, stats
 
+    def assign_strands(self, centres, queries, sim=0.0, strands=MC_STRAND_PLUS | MC_STRAND_MINUS):
+        """mc_assign_strands: assign() on the strand set ``strands`` (MC_STRAND_PLUS, MC_STRAND_MINUS
+        or both) -> (best, best_val, strand (0 plus, 1 minus), n_similar, stats).  With both strands
+        the minus strand wins a query only with a strictly larger combo 0; n_similar adds up."""
+        centres = np.ascontiguousarray(centres, np.uint32)
+        queries = np.ascontiguousarray(queries, np.uint32)
+        m = len(queries)
+        best = np.full(m, ASSIGN_NONE, np.uint32)
+        val = np.full(m, -1.0)
+        strand = np.zeros(m, np.uint8)
+        nsim = np.zeros(m, np.uint32)
+        stats = np.zeros(3, np.uint64)
+        _check(self.lib.mc_assign_strands(self.ctx, _p(centres), len(centres), _p(queries), m, float(sim), int(strands),
+                                          _p(best), _p(val), _p(strand), _p(nsim), _p(stats)), "mc_assign_strands")
+        return best, val, strand, nsim, stats
+
+    def revcomp_rows(self, ids):
+        """mc_revcomp_rows: the histogram rows of the points ``ids`` permuted to the other strand
+        (row[rc(i)]: the histograms of the reverse-complemented records), shape (len(ids), 4^k)."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        dt = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[self.width]
+        rows = np.zeros((len(ids), self.B), dt)
+        _check(self.lib.mc_revcomp_rows(self.ctx, _p(ids), len(ids), _p(rows)), "mc_revcomp_rows")
+        return rows
+
     def classify_values(self, raw):
         """raw: (m, n_single) precomputed single-feature values -> (similar, combo0, sum)."""
         raw = np.ascontiguousarray(raw, np.float64)
@@ -349,18 +382,25 @@ class Engine:
         return {f: (out[2 * i], int(out[2 * i + 1])) for i, f in enumerate(FAMILIES)}
 
 
-def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8):
+def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False):
     """Place the reads of the FASTA file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
-    similar centres) and, if given, the unassigned reads as FASTA; returns the stats dict."""
+    similar centres) and, if given, the unassigned reads as FASTA; returns the stats dict.
+    ``both_strands``: meshclust-assign's --both-strands (mcl_assign_strands): every read is scored
+    as written and reverse-complemented, the TSV gains a strand column (+, -, * unassigned) and
+    the stats ``strands`` and ``assigned_minus``."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    rc = lib.mcl_assign(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
-                        unassigned.encode() if unassigned else None, buf, len(buf))
+    if both_strands:
+        rc = lib.mcl_assign_strands(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                    unassigned.encode() if unassigned else None, 1, buf, len(buf))
+    else:
+        rc = lib.mcl_assign(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                            unassigned.encode() if unassigned else None, buf, len(buf))
     st = json.loads(buf.value.decode() or "{}")
     if rc != 0 or "error" in st:
         raise MCError("mcl_assign failed (%d): %s" % (rc, st.get("error", st)))

@@ -21,6 +21,13 @@
 // LDS tile: entry e = nch row chunks + 3 info chunks, at tile[e * (nch + 3)]:
 //   short    {mag, len, ap | ~0 (PSm not ok), np}, {da, kq = mag - B ap}, {gate lo, gate hi}
 //   general  {mag, sumsq}, {len, gate lo}, {gate hi, -}
+// Both kernels are templates on the strand set (mc_assign_strands; mc_assign is plus alone).  The
+// histogram of a reverse-complemented record is its row permuted by rc_index (host/strand.hpp),
+// and every scorer input is a bin-wise sum, so score(rc(query), centre) == score(query,
+// rc(centre)): revcomp_rows_kernel permutes the C centre rows once per call.  Minus alone reads
+// the tile rows from that buffer; with both strands an entry is the forward row, the permuted row
+// and the same 3 info chunks, at tile[e * (2 nch + 3)], each strand keeps its own running result
+// and the two are combined at the end (minus wins only with a strictly larger combo 0).
 // Every scorer here is one of features.hpp's (classify_small / classify_std / classify_raw),
 // which return the same decision and combo 0 bit for bit, so the result equals what
 // mc_classify_pairs gives for the same pair.
@@ -29,6 +36,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../host/strand.hpp"
 #include "features.hpp"
 
 namespace mcg {
@@ -52,7 +60,46 @@ struct AssignArgs {
   double *bval;
   uint32_t *nsim;
   unsigned long long *stats;  // {candidate pairs, classify_std fall-backs}
+  // strands (mc_assign_strands): the centres' permuted rows, row j for centre_ids[j], at the
+  // histograms' pitch; with both strands the minus strand's running result between tiles
+  // (general form) and the strand of the final result
+  const uint8_t *rc;
+  uint32_t *best_m;
+  double *bval_m;
+  uint32_t *nsim_m;
+  uint8_t *strand;
 };
+
+// S is the strand set (MC_STRAND_PLUS, MC_STRAND_MINUS or both): rows per tile entry
+template <int S>
+constexpr int rows_of = S == (MC_STRAND_PLUS | MC_STRAND_MINUS) ? 2 : 1;
+
+// The two strands' running results change places: the entry loop scores into one set and swaps
+// after every pass, so after the two passes of an entry both are back in place.
+__device__ __forceinline__ void swap_strands(double &bv, uint32_t &bj, uint32_t &ns, double &bvm, uint32_t &bjm,
+                                             uint32_t &nsm) {
+  const double v = bv;
+  bv = bvm;
+  bvm = v;
+  const uint32_t j = bj, n = ns;
+  bj = bjm;
+  bjm = j;
+  ns = nsm;
+  nsm = n;
+}
+
+// Both strands' results of one query into one: the minus strand wins only with a strictly larger
+// combo 0 (or when the plus strand has no similar centre); the counts add.
+__device__ __forceinline__ uint32_t combine_strands(double &bv, uint32_t &bj, uint32_t &ns, double bvm, uint32_t bjm,
+                                                    uint32_t nsm) {
+  const bool minus = bjm != NONE && (bj == NONE || bvm > bv);
+  if (minus) {
+    bv = bvm;
+    bj = bjm;
+  }
+  ns += nsm;
+  return minus ? 1u : 0u;
+}
 
 __device__ __forceinline__ PInfo pinfo(const HistView &H, uint32_t id) {
   return PInfo{H.mag[id], H.sumsq[id], H.len[id]};
@@ -63,22 +110,30 @@ __device__ __forceinline__ uint4 pack2(uint64_t a, uint64_t b) {
 __device__ __forceinline__ uint64_t lo64(const uint4 &v) { return (uint64_t)v.x | ((uint64_t)v.y << 32); }
 __device__ __forceinline__ uint64_t hi64(const uint4 &v) { return (uint64_t)v.z | ((uint64_t)v.w << 32); }
 
-// the rows of centres c0 .. c0 + cn into the tile (every thread of the workgroup)
+// the rows of centres c0 .. c0 + cn into the tile (every thread of the workgroup): the forward
+// row, the permuted row, or the forward row followed by the permuted one
+template <int S>
 __device__ __forceinline__ void load_tile_rows(const AssignArgs &A, uint4 *tl, uint32_t c0, uint32_t cn, int nch) {
-  const uint32_t ent = (uint32_t)nch + INFO;
+  const uint32_t ent = (uint32_t)(rows_of<S> * nch) + INFO;
   for (uint32_t t = threadIdx.x; t < cn * (uint32_t)nch; t += NT) {
     const uint32_t cc = t / (uint32_t)nch, ch = t % (uint32_t)nch;
-    tl[cc * ent + ch] = reinterpret_cast<const uint4 *>(A.H.hist + (uint64_t)A.cid[c0 + cc] * A.H.pitch)[ch];
+    if (S & MC_STRAND_PLUS)
+      tl[cc * ent + ch] = reinterpret_cast<const uint4 *>(A.H.hist + (uint64_t)A.cid[c0 + cc] * A.H.pitch)[ch];
+    if (S & MC_STRAND_MINUS)
+      tl[cc * ent + (rows_of<S> - 1) * nch + ch] =
+          reinterpret_cast<const uint4 *>(A.rc + (uint64_t)(c0 + cc) * A.H.pitch)[ch];
   }
 }
 
 // -------------------------------------------------------------------- short form
+template <int S>
 __global__ __launch_bounds__(NT) void assign_short_kernel(AssignArgs A, DevClassifier C, FastCls F) {
   extern __shared__ __attribute__((aligned(16))) uint4 tl[];
   __shared__ SmallK s_sk;
   const HistView &H = A.H;
   const int nch = (H.B + 15) / 16;
-  const uint32_t ent = (uint32_t)nch + INFO;
+  constexpr int NR = rows_of<S>;
+  const uint32_t ent = (uint32_t)(NR * nch) + INFO;
   if (threadIdx.x == 0) s_sk = make_smallk(C, F);
   const uint64_t i = (uint64_t)blockIdx.x * NT + threadIdx.x;
   const bool valid = i < A.M;
@@ -97,41 +152,48 @@ __global__ __launch_bounds__(NT) void assign_short_kernel(AssignArgs A, DevClass
     lenq = pq.len;
   }
   const double dap = C.layout == 4 ? mk_div((double)ps.mag, (double)H.B, F.rB) : 0.0;
-  double bv = -1.0;
-  uint32_t bj = NONE, ns = 0, ncand = 0, nfb = 0;
+  double bv = -1.0, bvm = -1.0;  // (the minus strand's running result: used with both strands only)
+  uint32_t bj = NONE, ns = 0, bjm = NONE, nsm = 0, ncand = 0, nfb = 0;
   for (uint32_t c0 = 0; c0 < A.C; c0 += A.tile) {
     const uint32_t cn = min(A.tile, A.C - c0);
     __syncthreads();  // (the previous tile's reads are done)
-    load_tile_rows(A, tl, c0, cn, nch);
+    load_tile_rows<S>(A, tl, c0, cn, nch);
     for (uint32_t t = threadIdx.x; t < cn; t += NT) {
       const uint32_t id = A.cid[c0 + t];
       const PInfo pc = pinfo(H, id);
       const PTerms tc = pterms_mk(pc.mag, pc.sumsq, H.B, F.rB);
       const PSm pm = psmall(pc, tc);
       const double kq = (double)((int64_t)pc.mag - (int64_t)H.B * tc.ap);
-      uint4 *info = tl + t * ent + nch;
+      uint4 *info = tl + t * ent + NR * nch;
       info[0] = make_uint4(pm.mag, pm.len, pm.ok ? pm.ap : ~0u, pm.np);
       info[1] = pack2(__builtin_bit_cast(uint64_t, tc.da), __builtin_bit_cast(uint64_t, kq));
       info[2] = pack2(A.glo[c0 + t], A.ghi[c0 + t]);
     }
     __syncthreads();
-    for (uint32_t e = 0; e < cn; e++) {
+    // Pass p scores row p % NR of entry p / NR against the query's registers (with both strands a
+    // second pass over the entry, not a second copy of the query).  (bv, bj, ns) is the running
+    // result of the strand being scored; the other one's waits in (bvm, bjm, nsm) and the two are
+    // swapped after every pass -- an entry is gated as a whole, so the passes stay in step.
+    for (uint32_t p = 0; p < cn * NR; p++) {
+      const uint32_t e = p / NR, r = p % NR;
       const uint4 *ce = tl + e * ent;  // (the same address in every lane: broadcast reads)
-      const uint4 g = ce[nch + 2];
+      const uint4 *ci = ce + NR * nch;  // (the info chunks: the same for both strands)
+      const uint4 *row = ce + r * nch;
+      const uint4 g = ci[2];
       const bool pass = valid && (!A.gate || (lo64(g) <= lenq && lenq <= hi64(g)));
       if (__ballot(pass) == 0) continue;  // (uniform: no lane of this wave passes the gate)
       Acc<uint8_t> acc;
 #pragma unroll
       for (int c = 0; c < 16; c++)
-        if (c < nch) acc.add(mine[c], ce[c]);
+        if (c < nch) acc.add(mine[c], row[c]);
       if (pass) {
-        ncand++;
-        const uint4 inf = ce[nch];
+        if (r == 0) ncand++;
+        const uint4 inf = ci[0];
         double cv = -1.0;
         int d = 0;
         bool und = true;
         if (ps.ok && inf.z != ~0u) {
-          const uint4 i1 = ce[nch + 1];
+          const uint4 i1 = ci[1];
           const SmallK sk = lds_smallk(&s_sk);
           const PSm pc{inf.x, inf.y, inf.z, inf.w, true};
           acc.fold();
@@ -153,12 +215,16 @@ __global__ __launch_bounds__(NT) void assign_short_kernel(AssignArgs A, DevClass
           }
         }
       }
+      if (NR == 2) swap_strands(bv, bj, ns, bvm, bjm, nsm);
     }
   }
+  uint32_t st = 0;
+  if (NR == 2) st = combine_strands(bv, bj, ns, bvm, bjm, nsm);
   if (valid) {
     A.best[i] = bj;
     A.bval[i] = bv;
     A.nsim[i] = ns;
+    if (NR == 2) A.strand[i] = (uint8_t)st;
   }
   ncand = wave_sum32_all(ncand);  // (<= 64 * C per wave)
   nfb = wave_sum32_all(nfb);
@@ -169,12 +235,13 @@ __global__ __launch_bounds__(NT) void assign_short_kernel(AssignArgs A, DevClass
 }
 
 // -------------------------------------------------------------------- general form
-template <typename T>
+template <typename T, int S>
 __global__ __launch_bounds__(NT) void assign_general_kernel(AssignArgs A, DevClassifier C) {
   extern __shared__ __attribute__((aligned(16))) uint4 tl[];
   const HistView &H = A.H;
   const int nch = (int)((H.B * (int)sizeof(T) + 15) / 16);
-  const uint32_t ent = (uint32_t)nch + INFO;
+  constexpr int NR = rows_of<S>;
+  const uint32_t ent = (uint32_t)(NR * nch) + INFO;
   const int lane = threadIdx.x & 63, group = lane >> 4, lig = lane & 15, wave = wave_id();
   const int rows_per_block = 16;  // 4 waves x 4 groups
   const int per = (nch + 15) / 16;
@@ -185,10 +252,10 @@ __global__ __launch_bounds__(NT) void assign_general_kernel(AssignArgs A, DevCla
   for (uint32_t c0 = 0; c0 < A.C; c0 += A.tile) {
     const uint32_t cn = min(A.tile, A.C - c0);
     __syncthreads();
-    load_tile_rows(A, tl, c0, cn, nch);
+    load_tile_rows<S>(A, tl, c0, cn, nch);
     for (uint32_t t = threadIdx.x; t < cn; t += NT) {
       const PInfo pc = pinfo(H, A.cid[c0 + t]);
-      uint4 *info = tl + t * ent + nch;
+      uint4 *info = tl + t * ent + NR * nch;
       info[0] = pack2(pc.mag, pc.sumsq);
       info[1] = pack2(pc.len, A.glo[c0 + t]);
       info[2] = pack2(A.ghi[c0 + t], 0);
@@ -209,28 +276,39 @@ __global__ __launch_bounds__(NT) void assign_general_kernel(AssignArgs A, DevCla
       const PTerms tq = pterms(pq.mag, pq.sumsq, H.B);
       // the query's running result: its output slots between tiles (this lane wrote them)
       const bool owner = valid && lig == 0;
-      double bv = -1.0;
-      uint32_t bj = NONE, ns = 0;
+      double bv = -1.0, bvm = -1.0;  // (the minus strand's: used with both strands only)
+      uint32_t bj = NONE, ns = 0, bjm = NONE, nsm = 0;
       if (owner && c0 > 0) {
         bv = A.bval[i];
         bj = A.best[i];
         ns = A.nsim[i];
+        if (NR == 2) {
+          bvm = A.bval_m[i];
+          bjm = A.best_m[i];
+          nsm = A.nsim_m[i];
+        }
       }
-      for (uint32_t e = 0; e < cn; e++) {
+      // Pass p scores row p % NR of entry p / NR.  (bv, bj, ns) is the running result of the strand
+      // being scored; with both strands the other one's waits in (bvm, bjm, nsm) and the two are
+      // swapped after every pass -- an entry is gated as a whole, so the passes stay in step.
+      for (uint32_t p = 0; p < cn * NR; p++) {
+        const uint32_t e = p / NR, r = p % NR;
         const uint4 *ce = tl + e * ent;
-        const uint4 i0 = ce[nch], i1 = ce[nch + 1], i2 = ce[nch + 2];
+        const uint4 *ci = ce + NR * nch;  // (the info chunks: the same for both strands)
+        const uint4 *crow = ce + r * nch;
+        const uint4 i0 = ci[0], i1 = ci[1], i2 = ci[2];
         const bool pass = valid && (!A.gate || (hi64(i1) <= pq.len && pq.len <= lo64(i2)));
         if (__ballot(pass) == 0) continue;  // (uniform)
         Acc<T> acc;
 #pragma unroll
         for (int u = 0; u < RCH; u++) {
           const int ch = lig + 16 * u;
-          if (u < per && ch < nch) acc.add(mine[u], ce[ch]);
+          if (u < per && ch < nch) acc.add(mine[u], crow[ch]);
         }
-        for (int ch = lig + 16 * RCH; ch < nch; ch += 16) acc.add(reinterpret_cast<const uint4 *>(row)[ch], ce[ch]);
+        for (int ch = lig + 16 * RCH; ch < nch; ch += 16) acc.add(reinterpret_cast<const uint4 *>(row)[ch], crow[ch]);
         acc.reduce16();
         if (pass && lig == 0) {
-          ncand++;
+          if (r == 0) ncand++;
           const PInfo pc{lo64(i0), hi64(i0), lo64(i1)};
           const PS s = acc.finish(pq.mag, pc.mag);
           double cv;
@@ -251,8 +329,18 @@ __global__ __launch_bounds__(NT) void assign_general_kernel(AssignArgs A, DevCla
             }
           }
         }
+        if (NR == 2) swap_strands(bv, bj, ns, bvm, bjm, nsm);
       }
       if (owner) {
+        if (NR == 2) {
+          if (c0 + cn == A.C) {  // the last tile: both strands' results into one
+            A.strand[i] = (uint8_t)combine_strands(bv, bj, ns, bvm, bjm, nsm);
+          } else {
+            A.best_m[i] = bjm;
+            A.bval_m[i] = bvm;
+            A.nsim_m[i] = nsm;
+          }
+        }
         A.best[i] = bj;
         A.bval[i] = bv;
         A.nsim[i] = ns;
@@ -263,25 +351,82 @@ __global__ __launch_bounds__(NT) void assign_general_kernel(AssignArgs A, DevCla
   if (lane == 0 && ncand) atomicAdd(&A.stats[0], (unsigned long long)ncand);
 }
 
-}  // namespace
+// -------------------------------------------------------------------- the other strand's rows
+// out row r = the row of point ids[r] permuted by rc_index: out[i] = row[rc_index(i)], the
+// histogram of the reverse-complemented record.  A gather with a stride of 4^(k-1)
+// between neighbouring output bins, so a workgroup stages the source row in LDS with full
+// 16-byte loads, a thread gathers the 16 / sizeof(T) bins of one output chunk from LDS, and the
+// stores are whole chunks in thread order.  Bins past B (a row shorter than a chunk) are zero.
+template <typename T>
+__global__ __launch_bounds__(NT) void revcomp_rows_kernel(HistView H, const uint32_t *ids, uint64_t m, uint8_t *out, int k) {
+  extern __shared__ __attribute__((aligned(16))) uint4 tl[];
+  constexpr int E = 16 / (int)sizeof(T);      // bins per chunk
+  constexpr int PW = 4 / (int)sizeof(T);      // bins per 32-bit word
+  const int nch = (int)(H.pitch / 16);        // (the pitch is the row rounded up to whole chunks)
+  const T *src = reinterpret_cast<const T *>(tl);
+  for (uint64_t r = blockIdx.x; r < m; r += gridDim.x) {
+    const uint4 *row = reinterpret_cast<const uint4 *>(H.hist + (uint64_t)ids[r] * H.pitch);
+    __syncthreads();  // (the previous row's reads are done)
+    for (int ch = threadIdx.x; ch < nch; ch += NT) tl[ch] = row[ch];
+    __syncthreads();
+    uint4 *orow = reinterpret_cast<uint4 *>(out + r * H.pitch);
+    for (int ch = threadIdx.x; ch < nch; ch += NT) {
+      uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int e = 0; e < E; e++) {
+        const int i = ch * E + e;
+        if (i < H.B) w[e / PW] |= (uint32_t)src[mc::rc_index((uint32_t)i, k)] << (8 * (int)sizeof(T) * (e % PW));
+      }
+      orow[ch] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  }
+}
 
-}  // namespace mcg
+// the permuted rows of the m points d_ids into d_out (m rows at the histograms' pitch)
+int launch_revcomp(mc_ctx *c, const HistView &H, const uint32_t *d_ids, uint64_t m, uint8_t *d_out) {
+  const unsigned grid = (unsigned)std::min<uint64_t>(m, 8192);
+  const size_t lds = (size_t)H.pitch;
+  if (c->width == 1) revcomp_rows_kernel<uint8_t><<<grid, NT, lds, c->stream>>>(H, d_ids, m, d_out, c->k);
+  else revcomp_rows_kernel<uint16_t><<<grid, NT, lds, c->stream>>>(H, d_ids, m, d_out, c->k);
+  MCG_CHECK(hipGetLastError());
+  return MC_OK;
+}
 
-using namespace mcg;
+template <int S>
+void launch_assign(mc_ctx *c, const AssignArgs &A, bool is_short, uint64_t M, size_t lds) {
+  if (is_short) {
+    FastCls F = c->fcls;
+    F.rB = 1.0 / (double)A.H.B;
+    const unsigned grid = (unsigned)((M + NT - 1) / NT);
+    assign_short_kernel<S><<<grid, NT, lds, c->stream>>>(A, c->cls, F);
+  } else {
+    const unsigned grid = (unsigned)std::min<uint64_t>((M + 15) / 16, 1024);
+    if (c->width == 1) assign_general_kernel<uint8_t, S><<<grid, NT, lds, c->stream>>>(A, c->cls);
+    else assign_general_kernel<uint16_t, S><<<grid, NT, lds, c->stream>>>(A, c->cls);
+  }
+}
 
-extern "C" int mc_assign(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
-                         double sim, uint32_t *best, double *best_val, uint32_t *n_similar, uint64_t *stats) {
+// mc_assign (strands = MC_STRAND_PLUS, strand NULL) and mc_assign_strands; `who` names the entry
+// in error messages
+int assign_impl(mc_ctx *c, const char *who, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
+                double sim, int strands, uint32_t *best, double *best_val, uint8_t *strand, uint32_t *n_similar,
+                uint64_t *stats) {
   if (!c || c->k == 0 || !c->has_cls) return MC_ERR_STATE;
+  const std::string w = who;
+  if (strands < MC_STRAND_PLUS || strands > (MC_STRAND_PLUS | MC_STRAND_MINUS)) {
+    set_error(w + ": strands must be MC_STRAND_PLUS, MC_STRAND_MINUS or both");
+    return MC_ERR_ARG;
+  }
   if (c->cls.align) {
-    set_error("mc_assign: an alignment-mode classifier has no k-mer scorer (use mc_nw_identity + mc_classify_values)");
+    set_error(w + ": an alignment-mode classifier has no k-mer scorer (use mc_nw_identity + mc_classify_values)");
     return MC_ERR_UNSUPPORTED;
   }
   if (c->width != 1 && c->width != 2) {
-    set_error("mc_assign: 32/64-bit histograms are not supported (use mc_classify_pairs)");
+    set_error(w + ": 32/64-bit histograms are not supported (use mc_classify_pairs)");
     return MC_ERR_UNSUPPORTED;
   }
   if (!centre_ids || C == 0 || (M > 0 && !query_ids)) {
-    set_error("mc_assign: no centres (or no query ids)");
+    set_error(w + ": no centres (or no query ids)");
     return MC_ERR_ARG;
   }
   for (uint32_t j = 0; j < C; j++)
@@ -296,11 +441,12 @@ extern "C" int mc_assign(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, cons
     }
   if (stats) stats[0] = stats[1] = stats[2] = 0;
   if (M == 0) return MC_OK;
+  const bool both = strands == (MC_STRAND_PLUS | MC_STRAND_MINUS);
   const HistView H = hist_view(c);
   const int nch = (int)((H.B * H.width + 15) / 16);
-  const size_t ent_bytes = (size_t)(nch + INFO) * 16;
+  const size_t ent_bytes = (size_t)((both ? 2 : 1) * nch + INFO) * 16;
   if (ent_bytes > TILE_BYTES) {
-    set_error("mc_assign: a histogram row does not fit an LDS tile (use mc_classify_pairs)");
+    set_error(w + ": a histogram row does not fit an LDS tile (use mc_classify_pairs)");
     return MC_ERR_UNSUPPORTED;
   }
   uint32_t tile = (uint32_t)std::min<size_t>(TILE_BYTES / ent_bytes, C);
@@ -340,28 +486,43 @@ extern "C" int mc_assign(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, cons
   A.nsim = (uint32_t *)((char *)c->s_f.p + res_off);
   A.stats = (unsigned long long *)((char *)c->s_f.p + 2 * res_off);
   A.bval = (double *)c->s_e.p;
+  A.rc = nullptr;
+  A.best_m = A.nsim_m = nullptr;
+  A.bval_m = nullptr;
+  A.strand = nullptr;
+  if (strands & MC_STRAND_MINUS) {
+    if (int rc = ensure(c->s_d, (size_t)C * H.pitch + 16)) return rc;
+    A.rc = (const uint8_t *)c->s_d.p;
+  }
+  if (both) {  // s_g: the minus strand's best, n_similar, then the strands; s_h: its values
+    if (int rc = ensure(c->s_g, 2 * res_off + (size_t)M + 16)) return rc;
+    if (int rc = ensure(c->s_h, (size_t)M * 8 + 16)) return rc;
+    A.best_m = (uint32_t *)c->s_g.p;
+    A.nsim_m = (uint32_t *)((char *)c->s_g.p + res_off);
+    A.strand = (uint8_t *)c->s_g.p + 2 * res_off;
+    A.bval_m = (double *)c->s_h.p;
+  }
   MCG_CHECK(hipMemcpyAsync(c->s_a.p, centre_ids, (size_t)C * 4, hipMemcpyHostToDevice, c->stream));
   MCG_CHECK(hipMemcpyAsync(c->s_b.p, query_ids, (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
   MCG_CHECK(hipMemcpyAsync(c->s_c.p, gate.data(), (size_t)C * 16, hipMemcpyHostToDevice, c->stream));
   MCG_CHECK(hipMemsetAsync(A.stats, 0, 16, c->stream));
   const size_t lds = (size_t)tile * ent_bytes;
   MCG_CHECK(hipEventRecord(c->ev0, c->stream));
-  if (is_short) {
-    FastCls F = c->fcls;
-    F.rB = 1.0 / (double)H.B;
-    const unsigned grid = (unsigned)((M + NT - 1) / NT);
-    assign_short_kernel<<<grid, NT, lds, c->stream>>>(A, c->cls, F);
-  } else {
-    const unsigned grid = (unsigned)std::min<uint64_t>((M + 15) / 16, 1024);
-    if (c->width == 1) assign_general_kernel<uint8_t><<<grid, NT, lds, c->stream>>>(A, c->cls);
-    else assign_general_kernel<uint16_t><<<grid, NT, lds, c->stream>>>(A, c->cls);
-  }
+  if (strands & MC_STRAND_MINUS)
+    if (int rc = launch_revcomp(c, H, A.cid, C, (uint8_t *)c->s_d.p)) return rc;
+  if (both) launch_assign<MC_STRAND_PLUS | MC_STRAND_MINUS>(c, A, is_short, M, lds);
+  else if (strands == MC_STRAND_MINUS) launch_assign<MC_STRAND_MINUS>(c, A, is_short, M, lds);
+  else launch_assign<MC_STRAND_PLUS>(c, A, is_short, M, lds);
   MCG_CHECK(hipGetLastError());
   MCG_CHECK(hipEventRecord(c->ev1, c->stream));
   unsigned long long cnt[2] = {0, 0};
   if (best) MCG_CHECK(hipMemcpyAsync(best, A.best, (size_t)M * 4, hipMemcpyDeviceToHost, c->stream));
   if (best_val) MCG_CHECK(hipMemcpyAsync(best_val, A.bval, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
   if (n_similar) MCG_CHECK(hipMemcpyAsync(n_similar, A.nsim, (size_t)M * 4, hipMemcpyDeviceToHost, c->stream));
+  if (strand) {
+    if (both) MCG_CHECK(hipMemcpyAsync(strand, A.strand, (size_t)M, hipMemcpyDeviceToHost, c->stream));
+    else memset(strand, strands == MC_STRAND_MINUS ? 1 : 0, (size_t)M);
+  }
   MCG_CHECK(hipMemcpyAsync(cnt, A.stats, 16, hipMemcpyDeviceToHost, c->stream));
   MCG_CHECK(hipStreamSynchronize(c->stream));
   float ms = 0;
@@ -372,5 +533,56 @@ extern "C" int mc_assign(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, cons
     stats[1] = cnt[1];
     stats[2] = (uint64_t)((double)ms * 1000.0 + 0.5);
   }
+  return MC_OK;
+}
+
+}  // namespace
+
+}  // namespace mcg
+
+using namespace mcg;
+
+extern "C" int mc_assign(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
+                         double sim, uint32_t *best, double *best_val, uint32_t *n_similar, uint64_t *stats) {
+  return assign_impl(c, "mc_assign", centre_ids, C, query_ids, M, sim, MC_STRAND_PLUS, best, best_val, nullptr, n_similar, stats);
+}
+
+extern "C" int mc_assign_strands(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
+                                 double sim, int strands, uint32_t *best, double *best_val, uint8_t *strand,
+                                 uint32_t *n_similar, uint64_t *stats) {
+  return assign_impl(c, "mc_assign_strands", centre_ids, C, query_ids, M, sim, strands, best, best_val, strand, n_similar,
+                     stats);
+}
+
+extern "C" int mc_revcomp_rows(mc_ctx *c, const uint32_t *ids, uint64_t m, void *rows) {
+  if (!c || c->k == 0) return MC_ERR_STATE;
+  if (c->width != 1 && c->width != 2) {
+    set_error("mc_revcomp_rows: 32/64-bit histograms are not supported");
+    return MC_ERR_UNSUPPORTED;
+  }
+  const HistView H = hist_view(c);
+  if (H.pitch + INFO * 16 > TILE_BYTES) {
+    set_error("mc_revcomp_rows: a histogram row does not fit an LDS tile");
+    return MC_ERR_UNSUPPORTED;
+  }
+  if (m > 0 && (!ids || !rows)) {
+    set_error("mc_revcomp_rows: no ids (or no output)");
+    return MC_ERR_ARG;
+  }
+  for (uint64_t i = 0; i < m; i++)
+    if (ids[i] >= c->n) {
+      set_error("point id out of range");
+      return MC_ERR_ARG;
+    }
+  if (m == 0) return MC_OK;
+  MCG_CHECK(hipSetDevice(c->device));
+  if (int rc = ensure(c->s_a, (size_t)m * 4 + 16)) return rc;
+  if (int rc = ensure(c->s_d, (size_t)m * H.pitch + 16)) return rc;
+  MCG_CHECK(hipMemcpyAsync(c->s_a.p, ids, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+  if (int rc = launch_revcomp(c, H, (const uint32_t *)c->s_a.p, m, (uint8_t *)c->s_d.p)) return rc;
+  const size_t rowb = (size_t)H.B * H.width;
+  MCG_CHECK(hipMemcpy2DAsync(rows, rowb, c->s_d.p, H.pitch, rowb, m, hipMemcpyDeviceToHost, c->stream));
+  MCG_CHECK(hipStreamSynchronize(c->stream));
+  flush_timers(c);
   return MC_OK;
 }

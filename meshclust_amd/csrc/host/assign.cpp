@@ -20,7 +20,8 @@ namespace mc {
 
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
-    "[--unassigned rest.fa] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n";
+    "[--unassigned rest.fa] [--both-strands] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
+    "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
   AssignOptions o;
@@ -37,6 +38,7 @@ AssignOptions parse_assign_options(int argc, char **argv) {
       o.threads = atoi(argv[++i]);
       if (o.threads <= 0) throw Error("Number of threads must be greater than 0.", 1);
     } else if (arg == "--quiet") o.quiet = true;
+    else if (arg == "--both-strands") o.both_strands = true;
     else {
       struct stat st;
       if (stat(argv[i], &st) == 0 && S_ISREG(st.st_mode)) o.reads.push_back(argv[i]);
@@ -113,6 +115,10 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
 #else
   threads = 1;
 #endif
+  bool by_pairs = getenv("MC_ASSIGN_PAIRS") && atoi(getenv("MC_ASSIGN_PAIRS")) != 0;
+  // the pair list has no permuted rows: never score one strand where two were asked for
+  const char *no_strands = "meshclust-assign: --both-strands needs the device kernel (mc_assign_strands), which does not apply here: ";
+  if (by_pairs && opt.both_strands) throw Error(std::string(no_strands) + "MC_ASSIGN_PAIRS is set", 2);
   const Model model = read_model(opt.model);
   if (model.align)
     throw Error("meshclust-assign: " + opt.model +
@@ -155,13 +161,22 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   t0 = std::chrono::steady_clock::now();
   std::vector<uint32_t> best(M, MC_ASSIGN_NONE), nsim(M, 0);
   std::vector<double> val(M, -1.0);
-  bool by_pairs = getenv("MC_ASSIGN_PAIRS") && atoi(getenv("MC_ASSIGN_PAIRS")) != 0;
+  std::vector<uint8_t> strand;
+  if (opt.both_strands) {
+    r.strands = MC_STRAND_PLUS | MC_STRAND_MINUS;
+    strand.assign(M, 0);
+  }
   if (!by_pairs) {
     std::vector<uint32_t> cid(C), qid(M);
     for (uint64_t j = 0; j < C; j++) cid[j] = (uint32_t)j;
     for (uint64_t q = 0; q < M; q++) qid[q] = (uint32_t)(C + q);
     uint64_t st[3] = {0, 0, 0};
-    const int rc = mc_assign(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, best.data(), val.data(), nsim.data(), st);
+    const int rc = opt.both_strands
+                       ? mc_assign_strands(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, r.strands, best.data(),
+                                           val.data(), strand.data(), nsim.data(), st)
+                       : mc_assign(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, best.data(), val.data(),
+                                   nsim.data(), st);
+    if (rc == MC_ERR_UNSUPPORTED && opt.both_strands) throw Error(std::string(no_strands) + mc_last_error(), 2);
     if (rc == MC_ERR_UNSUPPORTED) {  // wide bins or rows: the pair list does the same job
       if (!opt.quiet) fprintf(stderr, "meshclust-assign: %s; scoring with mc_classify_pairs\n", mc_last_error());
       by_pairs = true;
@@ -177,7 +192,8 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   r.assign_ms = ms_since(t0);
   t0 = std::chrono::steady_clock::now();
   // one line per read, in input order: read header, centre header or *, cluster index or -1,
-  // combo 0, similar centres (headers without their '>')
+  // combo 0, similar centres (headers without their '>'); with both strands a sixth column: the
+  // strand the read was assigned on (+ or -), or * for an unassigned read
   std::string out;
   std::vector<uint32_t> rest;
   char num[64];
@@ -187,8 +203,14 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
     out += '\t';
     if (has) out.append(ds.headers[best[q]].substr(1));
     else out += '*';
-    snprintf(num, sizeof num, "\t%d\t%.17g\t%u\n", has ? (int)best[q] : -1, val[q], nsim[q]);
+    snprintf(num, sizeof num, "\t%d\t%.17g\t%u", has ? (int)best[q] : -1, val[q], nsim[q]);
     out += num;
+    if (opt.both_strands) {
+      out += '\t';
+      out += !has ? '*' : strand[q] ? '-' : '+';
+      if (has && strand[q]) r.assigned_minus++;
+    }
+    out += '\n';
     if (has) r.assigned++;
     else rest.push_back((uint32_t)(C + q));
   }
@@ -202,13 +224,15 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
 }
 
 std::string assign_stats_json(const AssignResult &r) {
-  char b[768];
+  char b[768], s[96] = "";  // (one strand: exactly the keys there were before --both-strands)
+  if (r.strands != MC_STRAND_PLUS)
+    snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
   snprintf(b, sizeof b,
-           "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, \"k\": %d, \"width\": %d, "
+           "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, %s\"k\": %d, \"width\": %d, "
            "\"path\": \"%s\", \"candidate_pairs\": %llu, \"fallback_pairs\": %llu, \"device_us\": %llu, "
            "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, \"write\": %.3f}}",
            (unsigned long long)r.reads, (unsigned long long)r.centres, (unsigned long long)r.assigned,
-           (unsigned long long)(r.reads - r.assigned), r.k, r.width, r.path.c_str(), (unsigned long long)r.candidates,
+           (unsigned long long)(r.reads - r.assigned), s, r.k, r.width, r.path.c_str(), (unsigned long long)r.candidates,
            (unsigned long long)r.fallbacks, (unsigned long long)r.device_us, r.parse_ms, r.upload_ms, r.kmer_ms,
            r.assign_ms, r.write_ms);
   return b;

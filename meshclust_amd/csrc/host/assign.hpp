@@ -14,6 +14,7 @@ struct AssignOptions {
   int device = 0;
   int threads = 0;  // 0 = OpenMP default
   bool quiet = false;
+  bool both_strands = false;  // --both-strands: score every read as written and reverse-complemented
 };
 
 struct AssignResult {
@@ -22,13 +23,17 @@ struct AssignResult {
   uint64_t fallbacks = 0;   // mc_assign: pairs decided by the full scorer
   uint64_t device_us = 0;   // mc_assign: kernel time from HIP events
   int k = 0, width = 0;
+  int strands = MC_STRAND_PLUS;  // MC_STRAND_PLUS, or both (3) with --both-strands
+  uint64_t assigned_minus = 0;   // both strands: reads assigned on their reverse complement
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
   double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, write_ms = 0;
 };
 
 // Throws mc::Error (bad options: code 1 with the usage text in what()).
 AssignOptions parse_assign_options(int argc, char **argv);
-// The whole job; writes the TSV (and the unassigned FASTA).  ctx NULL: a context on opt.device is
+// The whole job; writes the TSV (and the unassigned FASTA).  With both_strands the TSV has a sixth
+// column (+, -, or * for an unassigned read); where only the pair list applies (MC_ASSIGN_PAIRS,
+// wide bins or rows) both_strands throws an Error of code 2: the pair list has no permuted rows.  ctx NULL: a context on opt.device is
 // opened once the model and the centres file are accepted, and closed at the end.
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
 std::string assign_stats_json(const AssignResult &r);

@@ -14,10 +14,11 @@ extern "C" {
 // (assign.hpp run_assign): writes the TSV to `tsv` and, if `unassigned` is non-NULL, the
 // unassigned reads as FASTA.  The JSON summary goes to stats (cap bytes).  Returns 0 or an
 // error code with {"error": ...} in stats; an error never ends the calling process.
-int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
-               const char *tsv, const char *unassigned, char *stats, int cap) {
+static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
+                        int threads, const char *tsv, const char *unassigned, bool both_strands, char *stats, int cap) {
   try {
     mc::AssignOptions opt;
+    opt.both_strands = both_strands;
     opt.model = model ? model : "";
     opt.centres = centres ? centres : "";
     for (int i = 0; i < nreads; i++) opt.reads.push_back(reads[i]);
@@ -39,6 +40,19 @@ int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *
     const mc::Error *me = dynamic_cast<const mc::Error *>(&e);
     return me && me->code ? me->code : 1;
   }
+}
+
+int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
+               const char *tsv, const char *unassigned, char *stats, int cap) {
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, false, stats, cap);
+}
+
+// mcl_assign with meshclust-assign's --both-strands when both_strands is non-zero (mc_assign_strands
+// on both strands): the TSV gains the strand column, the summary "strands" and "assigned_minus".
+// Where only the pair list applies it returns 2 with the reason in stats.
+int mcl_assign_strands(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
+                       int threads, const char *tsv, const char *unassigned, int both_strands, char *stats, int cap) {
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, stats, cap);
 }
 
 // Records ids[0..n) of a parsed dataset (mcl_parse) as FASTA: header lines unchanged, each

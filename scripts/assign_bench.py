@@ -14,6 +14,11 @@ Both results are compared for equality first.  Prints one JSON line: both times,
 candidate pairs per second, bytes and operations per pair from the shape, and the kernel's share
 of its bound (which bound is named in the line).
 
+--both-strands also times mc_assign_strands on both strands in every round, right after the
+one-strand call, and adds its device time, the spread of both and their ratio to the line.  Its
+result is checked first against the header's rule applied in numpy to the one-strand results
+of mc_assign_strands (plus alone must equal mc_assign).
+
 Under rocprofv3 set MC_ACCUM_PLAIN_LAUNCH=1, as scripts/prof_round.sh does: the clustering's
 cooperative launch otherwise faults the profiler's exit handler, after the
 profile is written.
@@ -81,6 +86,8 @@ def main():
                          "reads, and the ratios are per candidate pair (config D: the whole pair list takes minutes)")
     ap.add_argument("--batch", type=int, default=1 << 22, help="pairs per mc_classify_pairs call")
     ap.add_argument("--id", type=float, default=0.90)
+    ap.add_argument("--both-strands", action="store_true",
+                    help="also time mc_assign_strands on both strands (the centres' permuted rows included)")
     a = ap.parse_args()
     n, templates, seed = bench.WORKLOADS[a.workload]
     fasta = bench.ensure_fasta(n, 1000, templates, 0.03, seed)
@@ -102,13 +109,29 @@ def main():
     k, width = st["k"], st["width"]
     B = 4 ** k
     nch = (B * width + 15) // 16
-    dev_us, dev_wall, pair_call, pair_dev_ms = [], [], [], []
+    dev_us, dev_wall, pair_call, pair_dev_ms, both_us, both_wall = [], [], [], [], [], []
     ref = None
     prounds = a.rounds if a.pairs_rounds is None else a.pairs_rounds
     for r in range(a.warmup + a.rounds):
         t0 = time.perf_counter()
         best, val, nsim, stats = eng.assign(centres, queries, a.id)
         wall = time.perf_counter() - t0
+        if a.both_strands:
+            t0 = time.perf_counter()
+            b3 = eng.assign_strands(centres, queries, a.id)
+            wall3 = time.perf_counter() - t0
+            if r == 0:
+                b1 = eng.assign_strands(centres, queries, a.id, M.MC_STRAND_PLUS)
+                b2 = eng.assign_strands(centres, queries, a.id, M.MC_STRAND_MINUS)
+                assert all(np.array_equal(x, y) for x, y in zip((b1[0], b1[1], b1[3]), (best, val, nsim))), "plus alone differs"
+                win = (b2[0] != M.ASSIGN_NONE) & ((b1[0] == M.ASSIGN_NONE) | (b2[1] > b1[1]))
+                want = (np.where(win, b2[0], b1[0]), np.where(win, b2[1], b1[1]), win.astype(np.uint8), b1[3] + b2[3])
+                assert all(np.array_equal(x, y) for x, y in zip(b3[:4], want)), "both strands differ from the rule"
+                assert int(b3[4][0]) == int(stats[0])
+                minus_wins, minus_similar = int(win.sum()), int((b2[3] > 0).sum())
+            if r >= a.warmup:
+                both_us.append(int(b3[4][2]))
+                both_wall.append(wall3)
         if r == 0 or r - a.warmup < prounds:
             eng.timers(reset=True)
             pb, pv, pn, pcand, t_call = pairs_pass(eng, centres, queries[:npq], lens, a.id, a.batch)
@@ -163,6 +186,18 @@ def main():
         "share_of_bound": round(cand / (d_us * 1e-6) / floor_pairs_s, 4) if floor_pairs_s else None,
         "outputs_equal": True,
     }
+    if a.both_strands:
+        b_us = float(np.median(both_us))
+        line.update({
+            "both_strands_device_us": b_us,
+            "both_strands_device_us_all": both_us,
+            "both_strands_call_wall_ms": round(1e3 * float(np.median(both_wall)), 3),
+            "both_over_plus_device_time": round(b_us / d_us, 3),
+            "both_strands_fallback_pairs": int(b3[4][1]),
+            "both_strands_minus_wins": minus_wins,
+            "both_strands_queries_similar_on_minus": minus_similar,
+            "both_strands_outputs_equal": True,
+        })
     print(json.dumps(line))
     eng.close()
 
