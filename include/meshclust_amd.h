@@ -247,6 +247,31 @@ int mc_assign_strands(mc_ctx *ctx, const uint32_t *centre_ids, uint32_t C, const
                       uint8_t *strand /* 0 plus, 1 minus; 0 when unassigned */, uint32_t *n_similar, uint64_t *stats);
 
 /*
+ * mc_assign_strands reporting the K best centres of every query instead of one.
+ * A HIT of query q is a (centre index j, strand s) whose pair passes the length gate and is
+ * classified similar: exactly the event that n_similar counts in mc_assign_strands.  With both
+ * strands one centre can give two hits.  Row q of hit / hit_val / hit_strand (K entries each)
+ * holds the first min(K, n_similar[q]) hits of q in THE ORDER
+ *   1. combo 0 descending,
+ *   2. then the plus strand (0) before the minus strand (1),
+ *   3. then the centre index j ascending;
+ * the remaining slots hold MC_ASSIGN_NONE, -1.0 and 0.  n_similar (not capped at K), stats, the
+ * gate, the strand sets and MC_ERR_UNSUPPORTED are mc_assign_strands'.  K = 0 or
+ * K > MC_ASSIGN_MAX_TOP is MC_ERR_ARG.  Any output pointer may be NULL.
+ * Column 0 at any K, and so the whole result at K = 1, is mc_assign_strands' best / best_val /
+ * strand: the largest value wins, a tie between strands goes to plus, a tie within a strand to
+ * the lowest index.  (One difference: on MC_STRAND_MINUS alone mc_assign_strands reports strand 1
+ * also for an unassigned query; here an empty slot's strand is 0.)
+ * Where the lane-per-query kernel applies the list is kept in registers (capacity 2, 4 or 8, the
+ * next one up from K); the 16-lanes-per-query kernel keeps it in the query's output row.
+ */
+#define MC_ASSIGN_MAX_TOP 8
+int mc_assign_top(mc_ctx *ctx, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
+                  double sim, int strands /* 1, 2 or 3 */, uint32_t K /* 1..MC_ASSIGN_MAX_TOP */,
+                  uint32_t *hit /* M*K */, double *hit_val /* M*K */, uint8_t *hit_strand /* M*K */,
+                  uint32_t *n_similar /* M */, uint64_t *stats /* 3 */);
+
+/*
  * Batched utility::GlobAlignE(seqA,0,la-1,seqB,0,lb-1,1,-1,2,1).getIdentity() on the loaded
  * sequences (GlobAlignE.cpp:123-305; called by Trainer::align, Trainer.cpp:15-31, and
  * Feature::align, Feature.cpp:221-243).  len/ids may be NULL.

@@ -29,6 +29,7 @@ FEAT_INTERSECTION, FEAT_PEARSON, FEAT_KULCZYNSKI2 = 16, 32, 1024
 COMBO_SQUARED, COMBO_SELF = 1, 2
 ASSIGN_NONE = 0xFFFFFFFF
 MC_STRAND_PLUS, MC_STRAND_MINUS = 1, 2
+ASSIGN_MAX_TOP = 8  # MC_ASSIGN_MAX_TOP
 ERR_ARG, ERR_UNSUPPORTED = 1, 6
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
@@ -94,7 +95,7 @@ def gpu_lib():
                      "mc_mean_shift", "mc_update_iteration", "mc_timers", "mc_classify_values", "mc_mean_shift_select", "mc_accumulate",
                      "mc_scan_part", "mc_scan_commit", "mc_comm_unique_id", "mc_comm_create", "mc_comm_allgather",
                      "mc_comm_stats", "mc_comm_destroy", "mc_sync", "mc_assign", "mc_assign_strands",
-                     "mc_revcomp_rows"):
+                     "mc_revcomp_rows", "mc_assign_top"):
             getattr(lib, name).restype = C.c_int
         lib.mc_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
         lib.mc_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -105,6 +106,8 @@ def gpu_lib():
         lib.mc_assign_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_double, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mc_revcomp_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.mc_assign_top.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_double, C.c_int,
+                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _gpu = lib
     return _gpu
 
@@ -137,6 +140,9 @@ def host_lib():
         lib.mcl_assign_strands.restype = C.c_int
         lib.mcl_assign_strands.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                            C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
+        lib.mcl_assign_top.restype = C.c_int
+        lib.mcl_assign_top.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                       C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -293,6 +299,23 @@ class Engine:
                                           _p(best), _p(val), _p(strand), _p(nsim), _p(stats)), "mc_assign_strands")
         return best, val, strand, nsim, stats
 
+    def assign_top(self, centres, queries, sim=0.0, strands=MC_STRAND_PLUS, k=ASSIGN_MAX_TOP):
+        """mc_assign_top: the ``k`` (1 .. ASSIGN_MAX_TOP) best similar centres of every query on the
+        strand set ``strands`` -> (hit (M, k), hit_val (M, k), hit_strand (M, k), n_similar, stats).
+        A row is ordered by combo 0 descending, then plus before minus, then centre index ascending;
+        its unused slots hold ASSIGN_NONE, -1.0 and 0.  n_similar is not capped at k."""
+        centres = np.ascontiguousarray(centres, np.uint32)
+        queries = np.ascontiguousarray(queries, np.uint32)
+        m, kk = len(queries), max(int(k), 0)
+        hit = np.full((m, kk), ASSIGN_NONE, np.uint32)
+        val = np.full((m, kk), -1.0)
+        strand = np.zeros((m, kk), np.uint8)
+        nsim = np.zeros(m, np.uint32)
+        stats = np.zeros(3, np.uint64)
+        _check(self.lib.mc_assign_top(self.ctx, _p(centres), len(centres), _p(queries), m, float(sim), int(strands), int(k),
+                                      _p(hit), _p(val), _p(strand), _p(nsim), _p(stats)), "mc_assign_top")
+        return hit, val, strand, nsim, stats
+
     def revcomp_rows(self, ids):
         """mc_revcomp_rows: the histogram rows of the points ``ids`` permuted to the other strand
         (row[rc(i)]: the histograms of the reverse-complemented records), shape (len(ids), 4^k)."""
@@ -382,20 +405,28 @@ class Engine:
         return {f: (out[2 * i], int(out[2 * i + 1])) for i, f in enumerate(FAMILIES)}
 
 
-def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False):
+def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None):
     """Place the reads of the FASTA file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
     similar centres) and, if given, the unassigned reads as FASTA; returns the stats dict.
     ``both_strands``: meshclust-assign's --both-strands (mcl_assign_strands): every read is scored
     as written and reverse-complemented, the TSV gains a strand column (+, -, * unassigned) and
-    the stats ``strands`` and ``assigned_minus``."""
+    the stats ``strands`` and ``assigned_minus``.
+    ``top`` and ``hits`` (given together): meshclust-assign's --top K --hits FILE (mcl_assign_top): the
+    file ``hits`` gets one line per hit of the ``top`` best similar centres of every read (read, rank,
+    centre, cluster index, combo 0, and the strand with ``both_strands``); the TSV does not change,
+    the stats gain ``top`` and ``hits``."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    if both_strands:
+    if top is not None or hits is not None:
+        rc = lib.mcl_assign_top(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
+                                hits.encode() if hits else None, buf, len(buf))
+    elif both_strands:
         rc = lib.mcl_assign_strands(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                     unassigned.encode() if unassigned else None, 1, buf, len(buf))
     else:

@@ -28,6 +28,10 @@
 // the tile rows from that buffer; with both strands an entry is the forward row, the permuted row
 // and the same 3 info chunks, at tile[e * (2 nch + 3)], each strand keeps its own running result
 // and the two are combined at the end (minus wins only with a strictly larger combo 0).
+// mc_assign_top reports the K best hits of a query instead of one: a single list for both strands,
+// ordered on insertion by (combo 0 descending, plus before minus), equal ones in arrival order,
+// which is index ascending (host/topk.hpp).  The short form holds it in the lane's registers
+// (capacity 2, 4 or 8 as a template parameter), the general form in the query's output row.
 // Every scorer here is one of features.hpp's (classify_small / classify_std / classify_raw),
 // which return the same decision and combo 0 bit for bit, so the result equals what
 // mc_classify_pairs gives for the same pair.
@@ -37,6 +41,7 @@
 #include <vector>
 
 #include "../host/strand.hpp"
+#include "../host/topk.hpp"
 #include "features.hpp"
 
 namespace mcg {
@@ -68,11 +73,21 @@ struct AssignArgs {
   double *bval_m;
   uint32_t *nsim_m;
   uint8_t *strand;
+  // the K best hits (mc_assign_top, K >= 2): row q of hit / hval / hstr holds K slots
+  uint32_t K;
+  uint32_t *hit;
+  double *hval;
+  uint8_t *hstr;
 };
 
 // S is the strand set (MC_STRAND_PLUS, MC_STRAND_MINUS or both): rows per tile entry
 template <int S>
 constexpr int rows_of = S == (MC_STRAND_PLUS | MC_STRAND_MINUS) ? 2 : 1;
+// the strand of the hits of pass r (row r of an entry) with strand set S
+template <int S>
+__device__ __forceinline__ uint32_t strand_of(uint32_t r) {
+  return S == (MC_STRAND_PLUS | MC_STRAND_MINUS) ? r : S == MC_STRAND_MINUS ? 1u : 0u;
+}
 
 // The two strands' running results change places: the entry loop scores into one set and swaps
 // after every pass, so after the two passes of an entry both are back in place.
@@ -126,7 +141,11 @@ __device__ __forceinline__ void load_tile_rows(const AssignArgs &A, uint4 *tl, u
 }
 
 // -------------------------------------------------------------------- short form
-template <int S>
+// KC is the capacity of the list of best hits: 1 is mc_assign / mc_assign_strands (one running
+// result per strand, combined at the end); 2, 4 or 8 is mc_assign_top: one list for both strands
+// in the lane's registers, ordered on insertion (host/topk.hpp), of which the first A.K slots are
+// stored.  ns then counts the hits of both strands and nothing is swapped.
+template <int S, int KC>
 __global__ __launch_bounds__(NT) void assign_short_kernel(AssignArgs A, DevClassifier C, FastCls F) {
   extern __shared__ __attribute__((aligned(16))) uint4 tl[];
   __shared__ SmallK s_sk;
@@ -154,6 +173,8 @@ __global__ __launch_bounds__(NT) void assign_short_kernel(AssignArgs A, DevClass
   const double dap = C.layout == 4 ? mk_div((double)ps.mag, (double)H.B, F.rB) : 0.0;
   double bv = -1.0, bvm = -1.0;  // (the minus strand's running result: used with both strands only)
   uint32_t bj = NONE, ns = 0, bjm = NONE, nsm = 0, ncand = 0, nfb = 0;
+  mc::TopK<KC> top;  // (KC > 1 only)
+  if (KC > 1) top.clear();
   for (uint32_t c0 = 0; c0 < A.C; c0 += A.tile) {
     const uint32_t cn = min(A.tile, A.C - c0);
     __syncthreads();  // (the previous tile's reads are done)
@@ -209,22 +230,37 @@ __global__ __launch_bounds__(NT) void assign_short_kernel(AssignArgs A, DevClass
         }
         if (d) {
           ns++;
-          if (bj == NONE || cv > bv) {  // (ascending j: a tie keeps the lowest index)
+          if constexpr (KC > 1) {
+            mc::topk_insert(top, cv, c0 + e, strand_of<S>(r));
+          } else if (bj == NONE || cv > bv) {  // (ascending j: a tie keeps the lowest index)
             bv = cv;
             bj = c0 + e;
           }
         }
       }
-      if (NR == 2) swap_strands(bv, bj, ns, bvm, bjm, nsm);
+      if (NR == 2 && KC == 1) swap_strands(bv, bj, ns, bvm, bjm, nsm);
     }
   }
-  uint32_t st = 0;
-  if (NR == 2) st = combine_strands(bv, bj, ns, bvm, bjm, nsm);
-  if (valid) {
-    A.best[i] = bj;
-    A.bval[i] = bv;
-    A.nsim[i] = ns;
-    if (NR == 2) A.strand[i] = (uint8_t)st;
+  if constexpr (KC > 1) {
+    if (valid) {
+#pragma unroll
+      for (int t = 0; t < KC; t++)
+        if ((uint32_t)t < A.K) {
+          A.hit[i * A.K + t] = top.j[t];
+          A.hval[i * A.K + t] = top.v[t];
+          A.hstr[i * A.K + t] = (uint8_t)top.strand(t);
+        }
+      A.nsim[i] = ns;
+    }
+  } else {
+    uint32_t st = 0;
+    if (NR == 2) st = combine_strands(bv, bj, ns, bvm, bjm, nsm);
+    if (valid) {
+      A.best[i] = bj;
+      A.bval[i] = bv;
+      A.nsim[i] = ns;
+      if (NR == 2) A.strand[i] = (uint8_t)st;
+    }
   }
   ncand = wave_sum32_all(ncand);  // (<= 64 * C per wave)
   nfb = wave_sum32_all(nfb);
@@ -235,7 +271,10 @@ __global__ __launch_bounds__(NT) void assign_short_kernel(AssignArgs A, DevClass
 }
 
 // -------------------------------------------------------------------- general form
-template <typename T, int S>
+// TOP (mc_assign_top): the list of best hits of a query lives in row q of the output buffers,
+// A.K slots, and the owner lane inserts into it in memory at the moment of a hit
+// (topk_insert_row); ns counts the hits of both strands and is all that waits in A.nsim.
+template <typename T, int S, bool TOP>
 __global__ __launch_bounds__(NT) void assign_general_kernel(AssignArgs A, DevClassifier C) {
   extern __shared__ __attribute__((aligned(16))) uint4 tl[];
   const HistView &H = A.H;
@@ -278,7 +317,15 @@ __global__ __launch_bounds__(NT) void assign_general_kernel(AssignArgs A, DevCla
       const bool owner = valid && lig == 0;
       double bv = -1.0, bvm = -1.0;  // (the minus strand's: used with both strands only)
       uint32_t bj = NONE, ns = 0, bjm = NONE, nsm = 0;
-      if (owner && c0 > 0) {
+      if constexpr (TOP) {
+        if (owner && c0 > 0) ns = A.nsim[i];
+        if (owner && c0 == 0)
+          for (uint32_t t = 0; t < A.K; t++) {  // empty slots
+            A.hit[i * A.K + t] = NONE;
+            A.hval[i * A.K + t] = -1.0;
+            A.hstr[i * A.K + t] = 0;
+          }
+      } else if (owner && c0 > 0) {
         bv = A.bval[i];
         bj = A.best[i];
         ns = A.nsim[i];
@@ -322,16 +369,24 @@ __global__ __launch_bounds__(NT) void assign_general_kernel(AssignArgs A, DevCla
             d = classify_raw(C, raw, &cv, nullptr);
           }
           if (d) {
-            ns++;
-            if (bj == NONE || cv > bv) {
-              bv = cv;
-              bj = c0 + e;
+            if constexpr (TOP) {  // (pass && lig == 0: the owner lane)
+              mc::topk_insert_row(A.hval + i * A.K, A.hit + i * A.K, A.hstr + i * A.K, A.K, min(ns, A.K), cv, c0 + e,
+                                  strand_of<S>(r));
+              ns++;
+            } else {
+              ns++;
+              if (bj == NONE || cv > bv) {
+                bv = cv;
+                bj = c0 + e;
+              }
             }
           }
         }
-        if (NR == 2) swap_strands(bv, bj, ns, bvm, bjm, nsm);
+        if (NR == 2 && !TOP) swap_strands(bv, bj, ns, bvm, bjm, nsm);
       }
-      if (owner) {
+      if constexpr (TOP) {
+        if (owner) A.nsim[i] = ns;
+      } else if (owner) {
         if (NR == 2) {
           if (c0 + cn == A.C) {  // the last tile: both strands' results into one
             A.strand[i] = (uint8_t)combine_strands(bv, bj, ns, bvm, bjm, nsm);
@@ -392,29 +447,45 @@ int launch_revcomp(mc_ctx *c, const HistView &H, const uint32_t *d_ids, uint64_t
   return MC_OK;
 }
 
+// A.K == 1: one result per query; A.K >= 2 (mc_assign_top): the short form's next capacity up
+// (2, 4 or 8), the general form's list in memory
 template <int S>
 void launch_assign(mc_ctx *c, const AssignArgs &A, bool is_short, uint64_t M, size_t lds) {
   if (is_short) {
     FastCls F = c->fcls;
     F.rB = 1.0 / (double)A.H.B;
     const unsigned grid = (unsigned)((M + NT - 1) / NT);
-    assign_short_kernel<S><<<grid, NT, lds, c->stream>>>(A, c->cls, F);
+    if (A.K == 1) assign_short_kernel<S, 1><<<grid, NT, lds, c->stream>>>(A, c->cls, F);
+    else if (A.K <= 2) assign_short_kernel<S, 2><<<grid, NT, lds, c->stream>>>(A, c->cls, F);
+    else if (A.K <= 4) assign_short_kernel<S, 4><<<grid, NT, lds, c->stream>>>(A, c->cls, F);
+    else assign_short_kernel<S, 8><<<grid, NT, lds, c->stream>>>(A, c->cls, F);
   } else {
     const unsigned grid = (unsigned)std::min<uint64_t>((M + 15) / 16, 1024);
-    if (c->width == 1) assign_general_kernel<uint8_t, S><<<grid, NT, lds, c->stream>>>(A, c->cls);
-    else assign_general_kernel<uint16_t, S><<<grid, NT, lds, c->stream>>>(A, c->cls);
+    if (A.K == 1) {
+      if (c->width == 1) assign_general_kernel<uint8_t, S, false><<<grid, NT, lds, c->stream>>>(A, c->cls);
+      else assign_general_kernel<uint16_t, S, false><<<grid, NT, lds, c->stream>>>(A, c->cls);
+    } else {
+      if (c->width == 1) assign_general_kernel<uint8_t, S, true><<<grid, NT, lds, c->stream>>>(A, c->cls);
+      else assign_general_kernel<uint16_t, S, true><<<grid, NT, lds, c->stream>>>(A, c->cls);
+    }
   }
 }
+static_assert(MC_ASSIGN_MAX_TOP == 8, "assign_short_kernel's largest capacity");
 
-// mc_assign (strands = MC_STRAND_PLUS, strand NULL) and mc_assign_strands; `who` names the entry
-// in error messages
+// mc_assign (strands = MC_STRAND_PLUS, strand NULL), mc_assign_strands (K = 1: best, best_val and
+// strand hold one entry per query) and mc_assign_top (K >= 2: they are the rows of hit, hit_val and
+// hit_strand, K entries per query); `who` names the entry in error messages
 int assign_impl(mc_ctx *c, const char *who, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
-                double sim, int strands, uint32_t *best, double *best_val, uint8_t *strand, uint32_t *n_similar,
+                double sim, int strands, uint32_t K, uint32_t *best, double *best_val, uint8_t *strand, uint32_t *n_similar,
                 uint64_t *stats) {
   if (!c || c->k == 0 || !c->has_cls) return MC_ERR_STATE;
   const std::string w = who;
   if (strands < MC_STRAND_PLUS || strands > (MC_STRAND_PLUS | MC_STRAND_MINUS)) {
     set_error(w + ": strands must be MC_STRAND_PLUS, MC_STRAND_MINUS or both");
+    return MC_ERR_ARG;
+  }
+  if (K < 1 || K > MC_ASSIGN_MAX_TOP) {
+    set_error(w + ": K must be 1 .. MC_ASSIGN_MAX_TOP");
     return MC_ERR_ARG;
   }
   if (c->cls.align) {
@@ -490,11 +561,24 @@ int assign_impl(mc_ctx *c, const char *who, const uint32_t *centre_ids, uint32_t
   A.best_m = A.nsim_m = nullptr;
   A.bval_m = nullptr;
   A.strand = nullptr;
+  A.K = K;
+  A.hit = nullptr;
+  A.hval = nullptr;
+  A.hstr = nullptr;
+  const bool top = K > 1;
+  const size_t hit_off = ((size_t)M * K * 4 + 15) / 16 * 16;
+  if (top) {  // s_g: the hits, then their strands; s_h: their values (no per-strand results here)
+    if (int rc = ensure(c->s_g, hit_off + (size_t)M * K + 16)) return rc;
+    if (int rc = ensure(c->s_h, (size_t)M * K * 8 + 16)) return rc;
+    A.hit = (uint32_t *)c->s_g.p;
+    A.hstr = (uint8_t *)c->s_g.p + hit_off;
+    A.hval = (double *)c->s_h.p;
+  }
   if (strands & MC_STRAND_MINUS) {
     if (int rc = ensure(c->s_d, (size_t)C * H.pitch + 16)) return rc;
     A.rc = (const uint8_t *)c->s_d.p;
   }
-  if (both) {  // s_g: the minus strand's best, n_similar, then the strands; s_h: its values
+  if (both && !top) {  // s_g: the minus strand's best, n_similar, then the strands; s_h: its values
     if (int rc = ensure(c->s_g, 2 * res_off + (size_t)M + 16)) return rc;
     if (int rc = ensure(c->s_h, (size_t)M * 8 + 16)) return rc;
     A.best_m = (uint32_t *)c->s_g.p;
@@ -516,10 +600,16 @@ int assign_impl(mc_ctx *c, const char *who, const uint32_t *centre_ids, uint32_t
   MCG_CHECK(hipGetLastError());
   MCG_CHECK(hipEventRecord(c->ev1, c->stream));
   unsigned long long cnt[2] = {0, 0};
-  if (best) MCG_CHECK(hipMemcpyAsync(best, A.best, (size_t)M * 4, hipMemcpyDeviceToHost, c->stream));
-  if (best_val) MCG_CHECK(hipMemcpyAsync(best_val, A.bval, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+  if (top) {
+    if (best) MCG_CHECK(hipMemcpyAsync(best, A.hit, (size_t)M * K * 4, hipMemcpyDeviceToHost, c->stream));
+    if (best_val) MCG_CHECK(hipMemcpyAsync(best_val, A.hval, (size_t)M * K * 8, hipMemcpyDeviceToHost, c->stream));
+    if (strand) MCG_CHECK(hipMemcpyAsync(strand, A.hstr, (size_t)M * K, hipMemcpyDeviceToHost, c->stream));
+  } else {
+    if (best) MCG_CHECK(hipMemcpyAsync(best, A.best, (size_t)M * 4, hipMemcpyDeviceToHost, c->stream));
+    if (best_val) MCG_CHECK(hipMemcpyAsync(best_val, A.bval, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+  }
   if (n_similar) MCG_CHECK(hipMemcpyAsync(n_similar, A.nsim, (size_t)M * 4, hipMemcpyDeviceToHost, c->stream));
-  if (strand) {
+  if (strand && !top) {
     if (both) MCG_CHECK(hipMemcpyAsync(strand, A.strand, (size_t)M, hipMemcpyDeviceToHost, c->stream));
     else memset(strand, strands == MC_STRAND_MINUS ? 1 : 0, (size_t)M);
   }
@@ -544,14 +634,32 @@ using namespace mcg;
 
 extern "C" int mc_assign(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
                          double sim, uint32_t *best, double *best_val, uint32_t *n_similar, uint64_t *stats) {
-  return assign_impl(c, "mc_assign", centre_ids, C, query_ids, M, sim, MC_STRAND_PLUS, best, best_val, nullptr, n_similar, stats);
+  return assign_impl(c, "mc_assign", centre_ids, C, query_ids, M, sim, MC_STRAND_PLUS, 1, best, best_val, nullptr, n_similar, stats);
 }
 
 extern "C" int mc_assign_strands(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
                                  double sim, int strands, uint32_t *best, double *best_val, uint8_t *strand,
                                  uint32_t *n_similar, uint64_t *stats) {
-  return assign_impl(c, "mc_assign_strands", centre_ids, C, query_ids, M, sim, strands, best, best_val, strand, n_similar,
-                     stats);
+  return assign_impl(c, "mc_assign_strands", centre_ids, C, query_ids, M, sim, strands, 1, best, best_val, strand,
+                     n_similar, stats);
+}
+
+// K >= 2: the kernels' list forms.  K = 1 is the one-result path itself (mc_assign_strands' kernels);
+// only the strand of an unassigned query on the minus strand alone differs: an empty slot holds 0.
+extern "C" int mc_assign_top(mc_ctx *c, const uint32_t *centre_ids, uint32_t C, const uint32_t *query_ids, uint64_t M,
+                             double sim, int strands, uint32_t K, uint32_t *hit, double *hit_val, uint8_t *hit_strand,
+                             uint32_t *n_similar, uint64_t *stats) {
+  std::vector<uint32_t> own;
+  if (K == 1 && strands == MC_STRAND_MINUS && hit_strand && !hit) {
+    own.resize(M);
+    hit = own.data();
+  }
+  const int rc = assign_impl(c, "mc_assign_top", centre_ids, C, query_ids, M, sim, strands, K, hit, hit_val, hit_strand,
+                             n_similar, stats);
+  if (rc == MC_OK && K == 1 && strands == MC_STRAND_MINUS && hit_strand)
+    for (uint64_t i = 0; i < M; i++)
+      if (hit[i] == MC_ASSIGN_NONE) hit_strand[i] = 0;
+  return rc;
 }
 
 extern "C" int mc_revcomp_rows(mc_ctx *c, const uint32_t *ids, uint64_t m, void *rows) {

@@ -15,13 +15,17 @@
 
 #include "fasta.hpp"
 #include "model.hpp"
+#include "topk.hpp"
 
 namespace mc {
 
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
-    "[--unassigned rest.fa] [--both-strands] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
-    "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n";
+    "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--device N] [--threads N] [--stats-json FILE] "
+    "[--quiet]\n"
+    "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
+    "  --top K --hits FILE  (given together, K = 1..8) also write the K best similar centres of every read to\n"
+    "                  FILE: read, rank, centre, cluster index, combo 0 (and the strand with --both-strands)\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
   AssignOptions o;
@@ -39,6 +43,11 @@ AssignOptions parse_assign_options(int argc, char **argv) {
       if (o.threads <= 0) throw Error("Number of threads must be greater than 0.", 1);
     } else if (arg == "--quiet") o.quiet = true;
     else if (arg == "--both-strands") o.both_strands = true;
+    else if (arg == "--top" && has) {
+      o.top = atoi(argv[++i]);
+      if (o.top < 1 || o.top > MC_ASSIGN_MAX_TOP)
+        throw Error(std::string("--top must be 1 .. ") + std::to_string(MC_ASSIGN_MAX_TOP) + "\n" + kUsage, 1);
+    } else if (arg == "--hits" && has) o.hits = argv[++i];
     else {
       struct stat st;
       if (stat(argv[i], &st) == 0 && S_ISREG(st.st_mode)) o.reads.push_back(argv[i]);
@@ -47,6 +56,7 @@ AssignOptions parse_assign_options(int argc, char **argv) {
   }
   if (o.model.empty() || o.centres.empty() || o.reads.empty())
     throw Error(std::string("--model, --centres and at least one reads file are required\n") + kUsage, 1);
+  if ((o.top > 0) != !o.hits.empty()) throw Error(std::string("--top K and --hits FILE are given together\n") + kUsage, 1);
   return o;
 }
 
@@ -56,9 +66,13 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
 
 // The same job through mc_classify_pairs: the candidate pairs of the length gate in batches,
 // the argmax on the host (largest combo 0 among the similar centres, lowest index on ties).
+// K > 0: also the K best similar centres of every query into rows of K slots (hit, hit_val), kept
+// in mc_assign_top's order by the insertion the kernels use (topk.hpp); one strand, so every
+// hit's strand is 0.
 static void assign_by_pairs(mc_ctx *ctx, const Dataset &ds, uint32_t C, uint64_t M, double sim,
                             std::vector<uint32_t> &best, std::vector<double> &val, std::vector<uint32_t> &nsim,
-                            uint64_t *candidates) {
+                            uint64_t *candidates, uint32_t K, std::vector<uint32_t> &hit, std::vector<double> &hit_val) {
+  std::vector<uint8_t> hit_strand((size_t)M * K, 0);
   std::vector<uint64_t> lo(C, 0), hi(C, ~0ull);
   if (sim > 0)
     for (uint32_t j = 0; j < C; j++) {
@@ -79,6 +93,8 @@ static void assign_by_pairs(mc_ctx *ctx, const Dataset &ds, uint32_t C, uint64_t
     for (size_t p = 0; p < a.size(); p++) {  // (pairs are query-major, centres ascending)
       if (!d[p]) continue;
       const uint64_t q = a[p] - C;
+      if (K > 0)
+        topk_insert_row(&hit_val[q * K], &hit[q * K], &hit_strand[q * K], K, std::min<uint32_t>(nsim[q], K), c0[p], b[p], 0);
       nsim[q]++;
       if (best[q] == MC_ASSIGN_NONE || c0[p] > val[q]) {
         best[q] = b[p];
@@ -166,12 +182,21 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
     r.strands = MC_STRAND_PLUS | MC_STRAND_MINUS;
     strand.assign(M, 0);
   }
+  // --top: rows of K slots per read, in mc_assign_top's order; the main TSV's row is rank 1
+  const uint32_t K = (uint32_t)opt.top;
+  r.top = opt.top;
+  std::vector<uint32_t> hit((size_t)M * K, MC_ASSIGN_NONE);
+  std::vector<double> hit_val((size_t)M * K, -1.0);
+  std::vector<uint8_t> hit_strand((size_t)M * K, 0);
   if (!by_pairs) {
     std::vector<uint32_t> cid(C), qid(M);
     for (uint64_t j = 0; j < C; j++) cid[j] = (uint32_t)j;
     for (uint64_t q = 0; q < M; q++) qid[q] = (uint32_t)(C + q);
     uint64_t st[3] = {0, 0, 0};
-    const int rc = opt.both_strands
+    const int rc = K > 0
+                       ? mc_assign_top(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, r.strands, K, hit.data(),
+                                       hit_val.data(), hit_strand.data(), nsim.data(), st)
+                   : opt.both_strands
                        ? mc_assign_strands(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, r.strands, best.data(),
                                            val.data(), strand.data(), nsim.data(), st)
                        : mc_assign(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, best.data(), val.data(),
@@ -182,12 +207,20 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
       by_pairs = true;
     } else {
       check(rc, "mc_assign");
+      if (K > 0)
+        for (uint64_t q = 0; q < M; q++) {
+          best[q] = hit[q * K];
+          val[q] = hit_val[q * K];
+          if (opt.both_strands) strand[q] = hit_strand[q * K];
+        }
       r.candidates = st[0];
       r.fallbacks = st[1];
       r.device_us = st[2];
     }
   }
-  if (by_pairs) assign_by_pairs(ctx, ds, (uint32_t)C, M, model.id, best, val, nsim, &r.candidates);
+  if (by_pairs) {
+    assign_by_pairs(ctx, ds, (uint32_t)C, M, model.id, best, val, nsim, &r.candidates, K, hit, hit_val);
+  }
   r.path = by_pairs ? "pairs" : "device";
   r.assign_ms = ms_since(t0);
   t0 = std::chrono::steady_clock::now();
@@ -219,14 +252,38 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
   if (fclose(f) != 0 || !ok) throw Error("cannot write " + opt.output, 1);
   if (!opt.unassigned.empty()) write_fasta(opt.unassigned, ds, rest.data(), rest.size());
+  if (K > 0) {
+    // one line per hit, reads in input order, ranks ascending: read header, rank (from 1), centre
+    // header, cluster index, combo 0; with both strands the hit's strand (+ or -)
+    out.clear();
+    for (uint64_t q = 0; q < M; q++)
+      for (uint32_t t = 0; t < K && hit[q * K + t] != MC_ASSIGN_NONE; t++) {
+        const uint32_t j = hit[q * K + t];
+        out.append(ds.headers[C + q].substr(1));
+        snprintf(num, sizeof num, "\t%u\t", t + 1);
+        out += num;
+        out.append(ds.headers[j].substr(1));
+        snprintf(num, sizeof num, "\t%u\t%.17g", j, hit_val[q * K + t]);
+        out += num;
+        if (opt.both_strands) out += hit_strand[q * K + t] ? "\t-" : "\t+";
+        out += '\n';
+        r.hits++;
+      }
+    FILE *h = fopen(opt.hits.c_str(), "w");
+    if (!h) throw Error("cannot write " + opt.hits + ": " + strerror(errno), 1);
+    const bool hok = fwrite(out.data(), 1, out.size(), h) == out.size();
+    if (fclose(h) != 0 || !hok) throw Error("cannot write " + opt.hits, 1);
+  }
   r.write_ms = ms_since(t0);
   return r;
 }
 
 std::string assign_stats_json(const AssignResult &r) {
-  char b[768], s[96] = "";  // (one strand: exactly the keys there were before --both-strands)
+  char b[896], s[192] = "";  // (one strand, no --top: exactly the keys there were before either option)
+  int n = 0;
   if (r.strands != MC_STRAND_PLUS)
-    snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
+    n = snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
+  if (r.top > 0) snprintf(s + n, sizeof s - n, "\"top\": %d, \"hits\": %llu, ", r.top, (unsigned long long)r.hits);
   snprintf(b, sizeof b,
            "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, %s\"k\": %d, \"width\": %d, "
            "\"path\": \"%s\", \"candidate_pairs\": %llu, \"fallback_pairs\": %llu, \"device_us\": %llu, "

@@ -15,6 +15,8 @@ struct AssignOptions {
   int threads = 0;  // 0 = OpenMP default
   bool quiet = false;
   bool both_strands = false;  // --both-strands: score every read as written and reverse-complemented
+  int top = 0;                // --top K (1..MC_ASSIGN_MAX_TOP) with --hits FILE: the K best centres per read
+  std::string hits;
 };
 
 struct AssignResult {
@@ -25,6 +27,8 @@ struct AssignResult {
   int k = 0, width = 0;
   int strands = MC_STRAND_PLUS;  // MC_STRAND_PLUS, or both (3) with --both-strands
   uint64_t assigned_minus = 0;   // both strands: reads assigned on their reverse complement
+  int top = 0;                   // --top: K, and the lines written to the hits file
+  uint64_t hits = 0;
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
   double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, write_ms = 0;
 };
@@ -35,6 +39,9 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // column (+, -, or * for an unassigned read); where only the pair list applies (MC_ASSIGN_PAIRS,
 // wide bins or rows) both_strands throws an Error of code 2: the pair list has no permuted rows.  ctx NULL: a context on opt.device is
 // opened once the model and the centres file are accepted, and closed at the end.
+// With top / hits (mc_assign_top; on the pair list the same ordered insertion on the host) the
+// hits file gets one line per hit (read, rank, centre, cluster index, combo 0, and the strand
+// with both_strands); the TSV is the one written without them.
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
 std::string assign_stats_json(const AssignResult &r);
 int assign_main(int argc, char **argv);

@@ -15,10 +15,15 @@ extern "C" {
 // unassigned reads as FASTA.  The JSON summary goes to stats (cap bytes).  Returns 0 or an
 // error code with {"error": ...} in stats; an error never ends the calling process.
 static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
-                        int threads, const char *tsv, const char *unassigned, bool both_strands, char *stats, int cap) {
+                        int threads, const char *tsv, const char *unassigned, bool both_strands, int top, const char *hits,
+                        char *stats, int cap) {
   try {
     mc::AssignOptions opt;
     opt.both_strands = both_strands;
+    opt.top = top;
+    if (hits) opt.hits = hits;
+    if (top < 0 || top > MC_ASSIGN_MAX_TOP || (top > 0) != !opt.hits.empty())
+      throw mc::Error("mcl_assign_top: top (1 .. MC_ASSIGN_MAX_TOP) and hits are given together", 1);
     opt.model = model ? model : "";
     opt.centres = centres ? centres : "";
     for (int i = 0; i < nreads; i++) opt.reads.push_back(reads[i]);
@@ -44,7 +49,7 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
 
 int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
                const char *tsv, const char *unassigned, char *stats, int cap) {
-  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, false, stats, cap);
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, false, 0, nullptr, stats, cap);
 }
 
 // mcl_assign with meshclust-assign's --both-strands when both_strands is non-zero (mc_assign_strands
@@ -52,7 +57,16 @@ int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *
 // Where only the pair list applies it returns 2 with the reason in stats.
 int mcl_assign_strands(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
                        int threads, const char *tsv, const char *unassigned, int both_strands, char *stats, int cap) {
-  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, stats, cap);
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, 0, nullptr, stats, cap);
+}
+
+// mcl_assign_strands with meshclust-assign's --top `top` --hits `hits` (mc_assign_top): the TSV is
+// unchanged, `hits` gets one line per hit of the `top` best similar centres of every read, the
+// summary gains "top" and "hits".  top = 0 with hits NULL is mcl_assign_strands.
+int mcl_assign_top(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
+                   const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, char *stats,
+                   int cap) {
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, stats, cap);
 }
 
 // Records ids[0..n) of a parsed dataset (mcl_parse) as FASTA: header lines unchanged, each

@@ -19,6 +19,13 @@ one-strand call, and adds its device time, the spread of both and their ratio to
 result is checked first against the header's rule applied in numpy to the one-strand results
 of mc_assign_strands (plus alone must equal mc_assign).
 
+--top K also times mc_assign_top in every round, at K = 1, 4, 8 (and K), on plus alone and, with
+--both-strands, on both strands, and adds their device times and their ratios to
+mc_assign_strands on the same strand set to the line.  Its plus-alone lists are checked first
+against a numpy reduction of the pair-list pass (every query's similar centres by combo 0
+descending, index ascending, cut at K) on the reads that pass covers; the both-strands lists
+against the merge, by the header's order, of the plus-alone and minus-alone lists.
+
 Under rocprofv3 set MC_ACCUM_PLAIN_LAUNCH=1, as scripts/prof_round.sh does: the clustering's
 cooperative launch otherwise faults the profiler's exit handler, after the
 profile is written.
@@ -41,9 +48,11 @@ import meshclust_amd as M  # noqa: E402
 SIMDS, CLOCK_HZ = 256 * 4, 2.4e9  # MI355X: 256 CUs x 4 SIMDs, ~2.4 GHz
 
 
-def pairs_pass(eng, centres, queries, lens, sim, batch):
+def pairs_pass(eng, centres, queries, lens, sim, batch, top=None):
     """The baseline: gate on the host, mc_classify_pairs per batch, argmax on the host.
-    Returns (best, val, nsim, candidate pairs, seconds inside mc_classify_pairs)."""
+    Returns (best, val, nsim, candidate pairs, seconds inside mc_classify_pairs).  ``top``: a pair
+    of arrays (len(queries), K) that receive every query's K best similar centres and their values
+    (combo 0 descending, index ascending; ASSIGN_NONE and -1.0 in the unused slots)."""
     C_ = len(centres)
     lc = lens[centres].astype(np.float64)
     lo = (lc * sim).astype(np.uint64)
@@ -72,6 +81,14 @@ def pairs_pass(eng, centres, queries, lens, sim, batch):
         best[q0:q0 + len(q)] = np.where(has, b, M.ASSIGN_NONE)
         val[q0:q0 + len(q)] = np.where(has, m[np.arange(len(q)), b], -1.0)
         nsim[q0:q0 + len(q)] = ns
+        if top is not None:
+            K = top[0].shape[1]
+            order = np.argsort(-m, axis=1, kind="stable")[:, :K]  # (a tie keeps the lower index first)
+            order = np.pad(order, ((0, 0), (0, K - order.shape[1])))  # (fewer centres than K)
+            v = np.take_along_axis(m, order, axis=1)
+            used = np.arange(K)[None, :] < np.minimum(ns, min(K, C_))[:, None]
+            top[0][q0:q0 + len(q)] = np.where(used, order, M.ASSIGN_NONE)
+            top[1][q0:q0 + len(q)] = np.where(used, v, -1.0)
     return best, val, nsim, cand, t_call
 
 
@@ -88,6 +105,8 @@ def main():
     ap.add_argument("--id", type=float, default=0.90)
     ap.add_argument("--both-strands", action="store_true",
                     help="also time mc_assign_strands on both strands (the centres' permuted rows included)")
+    ap.add_argument("--top", type=int, default=0, metavar="K",
+                    help="also time mc_assign_top at K = 1, 4, 8 and K (plus alone; with --both-strands both strands too)")
     a = ap.parse_args()
     n, templates, seed = bench.WORKLOADS[a.workload]
     fasta = bench.ensure_fasta(n, 1000, templates, 0.03, seed)
@@ -110,6 +129,9 @@ def main():
     B = 4 ** k
     nch = (B * width + 15) // 16
     dev_us, dev_wall, pair_call, pair_dev_ms, both_us, both_wall = [], [], [], [], [], []
+    top_ks = sorted({1, 4, 8, a.top}) if a.top else []
+    top_us = {(s, K): [] for K in top_ks for s in ([1, 3] if a.both_strands else [1])}
+    plus_us, top_lists = [], {}
     ref = None
     prounds = a.rounds if a.pairs_rounds is None else a.pairs_rounds
     for r in range(a.warmup + a.rounds):
@@ -132,9 +154,41 @@ def main():
             if r >= a.warmup:
                 both_us.append(int(b3[4][2]))
                 both_wall.append(wall3)
+        if a.top:
+            p1 = eng.assign_strands(centres, queries, a.id, M.MC_STRAND_PLUS)  # the same entry, the same strand set
+            if r >= a.warmup:
+                plus_us.append(int(p1[4][2]))
+            for (s, K), us in top_us.items():
+                t = eng.assign_top(centres, queries, a.id, s, K)
+                if r >= a.warmup:
+                    us.append(int(t[4][2]))
+                if r == 0:
+                    top_lists[(s, K)] = t
+                    one = p1 if s == 1 else b3
+                    assert all(np.array_equal(x[:, 0], y) for x, y in zip(t[:3], one[:3])), "column 0 differs from mc_assign_strands"
+                    assert np.array_equal(t[3], one[3]) and int(t[4][0]) == int(one[4][0])
+            if r == 0 and a.both_strands:  # both strands: the merge of the one-strand lists, by the header's order
+                K8 = M.ASSIGN_MAX_TOP
+                tp, tm = top_lists[(1, 8)], eng.assign_top(centres, queries, a.id, M.MC_STRAND_MINUS, K8)
+                hj, hv, hs = (np.concatenate([x, y], axis=1) for x, y in zip(tp[:3], tm[:3]))
+                empty = hj == M.ASSIGN_NONE
+                order = np.lexsort((hj, hs, -hv, empty), axis=-1)  # (empty slots last)
+                hj, hv, hs = (np.take_along_axis(x, order, axis=1) for x in (hj, hv, hs))
+                for K in top_ks:
+                    t = top_lists[(3, K)]
+                    assert all(np.array_equal(x, y[:, :K]) for x, y in zip(t[:3], (hj, hv, hs))), "both-strands lists differ from the merge"
+                    assert np.array_equal(t[3], tp[3] + tm[3])
         if r == 0 or r - a.warmup < prounds:
             eng.timers(reset=True)
-            pb, pv, pn, pcand, t_call = pairs_pass(eng, centres, queries[:npq], lens, a.id, a.batch)
+            ptop = (np.zeros((npq, max(top_ks)), np.uint32), np.zeros((npq, max(top_ks)))) if a.top and r == 0 else None
+            pb, pv, pn, pcand, t_call = pairs_pass(eng, centres, queries[:npq], lens, a.id, a.batch, ptop)
+            if ptop is not None:
+                for K in top_ks:
+                    t = top_lists[(1, K)]
+                    assert np.array_equal(t[0][:npq], ptop[0][:, :K]) and np.array_equal(t[1][:npq], ptop[1][:, :K]), \
+                        "mc_assign_top differs from the pair list's reduction"
+                    assert not t[2].any() and np.array_equal(t[3][:npq], pn)
+                top_truncated = {K: int((pn > K).sum()) for K in top_ks}
             pdev = eng.timers()["pairs"][0]
             assert np.array_equal(best[:npq], pb) and np.array_equal(val[:npq], pv) and np.array_equal(nsim[:npq], pn), \
                 "outputs differ"
@@ -198,6 +252,17 @@ def main():
             "both_strands_queries_similar_on_minus": minus_similar,
             "both_strands_outputs_equal": True,
         })
+    if a.top:
+        line["top_plus_alone_assign_strands_device_us"] = float(np.median(plus_us))
+        line["top_plus_alone_assign_strands_device_us_all"] = plus_us
+        line["top_reads_with_more_than_K_similar"] = {str(K): n for K, n in top_truncated.items()}
+        for (s, K), us in top_us.items():
+            name = "top_%s_K%d" % ("plus" if s == 1 else "both", K)
+            base = float(np.median(plus_us)) if s == 1 else float(np.median(both_us))
+            line[name + "_device_us"] = float(np.median(us))
+            line[name + "_device_us_all"] = us
+            line[name + "_over_assign_strands"] = round(float(np.median(us)) / base, 3)
+        line["top_outputs_equal"] = True
     print(json.dumps(line))
     eng.close()
 
