@@ -285,6 +285,44 @@ int mc_nw_identity_raw(mc_ctx *ctx, const uint8_t *a, const uint64_t *a_off, con
                        int32_t *ids, int32_t *score);
 
 /*
+ * THE MINUS-STRAND STRING of a point is its expanded byte string (what mc_nw_identity reads: 0..3
+ * inside segments, 'N' or the raw upper-case byte outside) reversed, every byte mapped: a digit
+ * d <= 3 becomes 3 - d, 'A' <-> 'T' and 'C' <-> 'G' (the raw letters of a record without
+ * segments), every other byte ('N' included) stays.  THE MINUS STRAND IS DEFINED AS THIS STRING,
+ * as it is defined as the permuted row above.  For a record of A, C, G, T and N it is the string
+ * the FASTA parser gives for the reverse-complemented record (the parser encodes every non-N byte
+ * of a record that has a segment, and none of a record that has none).  The map is an
+ * involution, so the minus strand of the minus strand is the string itself.
+ * mc_revcomp_sequences: the minus-strand strings of the points ids, concatenated; off[m+1] byte
+ * offsets into bytes (no padding at the ABI).  bytes may be NULL to get the offsets only.
+ * No sequences loaded is MC_ERR_STATE, an id >= n MC_ERR_ARG.
+ */
+int mc_revcomp_sequences(mc_ctx *ctx, const uint32_t *ids, uint64_t m, uint8_t *bytes, uint64_t *off);
+
+/*
+ * mc_nw_identity with a strand per pair: pair i aligns seq1 = point a[i] as written
+ * (a_minus[i] == 0) or its minus-strand string (a_minus[i] != 0) against seq2 = point b[i] as
+ * written.  a_minus == NULL is all plus.  With no minus pair the results are mc_nw_identity's bit
+ * for bit.  The read is the operand that is reverse-complemented, never the centre: GlobAlignE's
+ * tie-breaks (M before X before Y, the first maximum) are not mirror-symmetric, so
+ * identity(rc(a), b) need not be identity(a, rc(b)).
+ * The pairs are worked in batches: per batch the distinct ids among its minus pairs are
+ * reverse-complemented once on the device (a read with K hits once, not K times) into a buffer
+ * the context owns, then one NW launch set runs for the minus pairs and one for the plus pairs,
+ * every result going to its pair's own slot.  A batch ends at MC_IDENT_BATCH_PAIRS pairs or
+ * before the read whose string would take the buffer past MC_IDENT_BATCH_BYTES (records padded
+ * to 16 bytes; a single longer read still gets its own batch), so the scratch stays bounded for
+ * any m.  Environment, read per call: MC_IDENT_BATCH=<pairs> lowers the pair cap.  Batching
+ * changes no result.  Errors are mc_nw_identity's: no sequences MC_ERR_STATE, an id >= n
+ * MC_ERR_ARG, m = 0 MC_OK.  len/ids may be NULL.  The alignments are timed as "nw", the
+ * reverse-complement kernel as "layout" (mc_timers).
+ */
+#define MC_IDENT_BATCH_PAIRS (1ull << 20)
+#define MC_IDENT_BATCH_BYTES (256ull << 20)
+int mc_nw_identity_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                           double *ident, int32_t *len, int32_t *ids);
+
+/*
  * Accumulation (ClusterFactory::accumulate, ClusterFactory.cpp:637-714).
  * The bvec of Runner.cpp:342-350 is only ever shrunk after insert_finalize, so the device
  * holds one static candidate order (bin-major, length-sorted within bins) plus an alive

@@ -95,7 +95,7 @@ def gpu_lib():
                      "mc_mean_shift", "mc_update_iteration", "mc_timers", "mc_classify_values", "mc_mean_shift_select", "mc_accumulate",
                      "mc_scan_part", "mc_scan_commit", "mc_comm_unique_id", "mc_comm_create", "mc_comm_allgather",
                      "mc_comm_stats", "mc_comm_destroy", "mc_sync", "mc_assign", "mc_assign_strands",
-                     "mc_revcomp_rows", "mc_assign_top"):
+                     "mc_revcomp_rows", "mc_assign_top", "mc_revcomp_sequences", "mc_nw_identity_strands"):
             getattr(lib, name).restype = C.c_int
         lib.mc_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
         lib.mc_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -108,6 +108,9 @@ def gpu_lib():
         lib.mc_revcomp_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.mc_assign_top.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_double, C.c_int,
                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mc_revcomp_sequences.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.mc_nw_identity_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
         _gpu = lib
     return _gpu
 
@@ -143,6 +146,10 @@ def host_lib():
         lib.mcl_assign_top.restype = C.c_int
         lib.mcl_assign_top.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                        C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
+        lib.mcl_assign_identity.restype = C.c_int
+        lib.mcl_assign_identity.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                            C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
+                                            C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -381,6 +388,31 @@ class Engine:
                "mc_nw_identity")
         return ident, ln, ids
 
+    def revcomp_sequences(self, ids):
+        """mc_revcomp_sequences: the minus-strand strings of the points ``ids`` (the expanded byte
+        string reversed, digits d -> 3 - d, A <-> T, C <-> G, anything else unchanged), concatenated
+        -> (bytes uint8, off uint64 of len(ids) + 1)."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        off = np.zeros(len(ids) + 1, np.uint64)
+        _check(self.lib.mc_revcomp_sequences(self.ctx, _p(ids), len(ids), None, _p(off)), "mc_revcomp_sequences")
+        out = np.zeros(int(off[-1]), np.uint8)
+        _check(self.lib.mc_revcomp_sequences(self.ctx, _p(ids), len(ids), _p(out), _p(off)), "mc_revcomp_sequences")
+        return out, off
+
+    def nw_identity_strands(self, a, b, a_minus=None):
+        """mc_nw_identity_strands: nw_identity with a strand per pair; where ``a_minus[i]`` is
+        non-zero seq1 is the minus-strand string of point a[i] -> (ident, len, ids)."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        am = None if a_minus is None else np.ascontiguousarray(a_minus, np.uint8)
+        assert am is None or len(am) == len(a)
+        ident = np.zeros(len(a))
+        ln = np.zeros(len(a), np.int32)
+        ids = np.zeros(len(a), np.int32)
+        _check(self.lib.mc_nw_identity_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(len(a)), _p(ident), _p(ln),
+                                               _p(ids)), "mc_nw_identity_strands")
+        return ident, ln, ids
+
     def nw_identity_raw(self, a_cat, a_off, b_cat, b_off):
         a_cat = np.ascontiguousarray(a_cat, np.uint8)
         b_cat = np.ascontiguousarray(b_cat, np.uint8)
@@ -405,7 +437,8 @@ class Engine:
         return {f: (out[2 * i], int(out[2 * i + 1])) for i, f in enumerate(FAMILIES)}
 
 
-def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None):
+def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None,
+                 identity=False, min_identity=None):
     """Place the reads of the FASTA file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
@@ -416,13 +449,23 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     ``top`` and ``hits`` (given together): meshclust-assign's --top K --hits FILE (mcl_assign_top): the
     file ``hits`` gets one line per hit of the ``top`` best similar centres of every read (read, rank,
     centre, cluster index, combo 0, and the strand with ``both_strands``); the TSV does not change,
-    the stats gain ``top`` and ``hits``."""
+    the stats gain ``top`` and ``hits``.
+    ``identity`` / ``min_identity``: meshclust-assign's --identity and --min-identity X
+    (mcl_assign_identity): every reported (read, centre, strand) is aligned, the TSV and the hits file
+    gain a last column with the identity (* for an unassigned read); with ``min_identity`` a read goes
+    to the first of its hits that aligns at that identity or more, else it is unassigned.  The stats
+    gain ``identity_pairs``, ``identity_cells``, ``rejected`` and the ``identity`` phase."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    if top is not None or hits is not None:
+    if identity or min_identity is not None:
+        rc = lib.mcl_assign_identity(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                     unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
+                                     hits.encode() if hits else None, 1 if identity else 0,
+                                     -1.0 if min_identity is None else float(min_identity), buf, len(buf))
+    elif top is not None or hits is not None:
         rc = lib.mcl_assign_top(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                 unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
                                 hits.encode() if hits else None, buf, len(buf))

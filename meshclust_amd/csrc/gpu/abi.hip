@@ -294,7 +294,7 @@ int mc_ctx_destroy(mc_ctx *c) {
                  &c->alive, &c->members, &c->member_keys, &c->partials, &c->scan_dev, &c->flags_out, &c->s_a, &c->s_b,
                  &c->s_c, &c->s_d, &c->s_e, &c->s_f, &c->s_g, &c->s_h, &c->s_i, &c->s_j, &c->s_k, &c->hs, &c->mag_s, &c->sumsq_s, &c->len_s, &c->ticket,
                  &c->msum, &c->ident_s, &c->al_a, &c->al_b, &c->al_out, &c->al_id, &c->ord_ids, &c->acc_out, &c->sp_words, &c->sp_keys,
-                 &c->sp_scr, &c->sp_nodes, &c->sp_nn, &c->sp_q, &c->sp_err, &c->u_off, &c->u_mem, &c->nw_items, &c->nw_gran})
+                 &c->sp_scr, &c->sp_nodes, &c->sp_nn, &c->sp_q, &c->sp_err, &c->u_off, &c->u_mem, &c->nw_items, &c->nw_gran, &c->rc_seq})
     release(*b);
   if (c->h_scan) (void)hipHostFree(c->h_scan);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -771,6 +771,135 @@ int mc_nw_identity_raw(mc_ctx *c, const uint8_t *a, const uint64_t *a_off, const
   MCG_CHECK(hipMemcpyAsync(dI, idx.data(), m * 4, hipMemcpyHostToDevice, c->stream));
   TRY(launch_nw(c, dA, dAo, dI, dB, dBo, dI, m, la, lb, dId, dL, dIds, dSc));
   TRY(download_parts(c, {{ident, dId, m * 8}, {len, dL, m * 4}, {ids, dIds, m * 4}, {score, dSc, m * 4}}, c->stream));
+  flush_timers(c);
+  return MC_OK;
+}
+
+// The minus-strand strings (host/revseq.hpp) of the u points ids into c->rc_seq, record r at
+// h_off[r] (filled here: lengths rounded up to 16).  ids go through c->s_h, the offsets through
+// c->s_i; the caller keeps ids and h_off alive until the stream is synchronized.
+static int revseq_batch(mc_ctx *c, const uint32_t *ids, uint32_t u, std::vector<uint64_t> &h_off) {
+  h_off.resize((size_t)u + 1);
+  h_off[0] = 0;
+  for (uint32_t r = 0; r < u; r++)
+    h_off[r + 1] = h_off[r] + (c->h_seq_off[ids[r] + 1] - c->h_seq_off[ids[r]] + 15) / 16 * 16;
+  TRY(ensure(c->rc_seq, h_off[u] + 16));
+  TRY(upload(c, c->s_h, ids, u, c->stream));
+  TRY(upload(c, c->s_i, h_off.data(), (size_t)u + 1, c->stream));
+  return launch_revseq(c, (const uint32_t *)c->s_h.p, u, (const uint64_t *)c->s_i.p, h_off[u], (uint8_t *)c->rc_seq.p);
+}
+
+int mc_revcomp_sequences(mc_ctx *c, const uint32_t *ids, uint64_t m, uint8_t *bytes, uint64_t *off) {
+  if (!c || !c->codes.p) return MC_ERR_STATE;
+  if (!off || (m && !ids)) return MC_ERR_ARG;
+  TRY(check_ids(c, ids, m));
+  off[0] = 0;
+  for (uint64_t i = 0; i < m; i++) off[i + 1] = off[i] + (c->h_seq_off[ids[i] + 1] - c->h_seq_off[ids[i]]);
+  if (!bytes || m == 0) return MC_OK;
+  MCG_CHECK(hipSetDevice(c->device));
+  std::vector<uint64_t> h_off;
+  std::vector<uint8_t> host;
+  for (uint64_t i0 = 0; i0 < m;) {  // batches of at most MC_IDENT_BATCH_BYTES of padded strings
+    uint64_t i1 = i0, pad = 0;
+    while (i1 < m && i1 - i0 < MC_IDENT_BATCH_PAIRS) {
+      const uint64_t need = (off[i1 + 1] - off[i1] + 15) / 16 * 16;
+      if (i1 > i0 && pad + need > MC_IDENT_BATCH_BYTES) break;
+      pad += need;
+      i1++;
+    }
+    TRY(revseq_batch(c, ids + i0, (uint32_t)(i1 - i0), h_off));
+    host.resize(pad);
+    if (pad) MCG_CHECK(hipMemcpyAsync(host.data(), c->rc_seq.p, pad, hipMemcpyDeviceToHost, c->stream));
+    MCG_CHECK(hipStreamSynchronize(c->stream));
+    for (uint64_t i = i0; i < i1; i++)
+      if (off[i + 1] > off[i]) memcpy(bytes + off[i], host.data() + h_off[i - i0], off[i + 1] - off[i]);
+    i0 = i1;
+  }
+  flush_timers(c);
+  return MC_OK;
+}
+
+int mc_nw_identity_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                           double *ident, int32_t *len, int32_t *ids) {
+  if (!c || !c->codes.p) return MC_ERR_STATE;
+  if (m == 0) return MC_OK;
+  MCG_CHECK(hipSetDevice(c->device));
+  TRY(check_ids(c, a, m));
+  TRY(check_ids(c, b, m));
+  uint64_t cap = MC_IDENT_BATCH_PAIRS;
+  if (const char *e = getenv("MC_IDENT_BATCH")) {  // (read per call: a test forces several batches)
+    const long long v = atoll(e);
+    if (v > 0 && (uint64_t)v < cap) cap = (uint64_t)v;
+  }
+  auto length = [&](uint32_t id) { return c->h_seq_off[id + 1] - c->h_seq_off[id]; };
+  constexpr uint32_t NO_SLOT = 0xffffffffu;
+  std::vector<uint32_t> slot;  // point id -> its string's slot in this batch's buffer
+  if (a_minus) slot.assign(c->n, NO_SLOT);
+  std::vector<uint32_t> uniq, ai, bi, out;
+  std::vector<uint64_t> h_off, a_off2, la[2], lb[2];
+  for (uint64_t i0 = 0; i0 < m;) {
+    // the batch [i0, i1): ends at the pair cap, or where one more read's string would not fit
+    uniq.clear();
+    uint64_t i1 = i0, pad = 0, nm = 0;
+    while (i1 < m && i1 - i0 < cap) {
+      if (a_minus && a_minus[i1]) {
+        if (slot[a[i1]] == NO_SLOT) {
+          const uint64_t need = (length(a[i1]) + 15) / 16 * 16;
+          if (!uniq.empty() && pad + need > MC_IDENT_BATCH_BYTES) break;
+          pad += need;
+          slot[a[i1]] = (uint32_t)uniq.size();
+          uniq.push_back(a[i1]);
+        }
+        nm++;
+      }
+      i1++;
+    }
+    const uint64_t mb = i1 - i0, np = mb - nm;
+    // the minus pairs first, then the plus pairs; every result goes to its pair's own slot
+    ai.resize(mb);
+    bi.resize(mb);
+    out.resize(mb);
+    for (int s = 0; s < 2; s++) {
+      la[s].clear();
+      lb[s].clear();
+    }
+    uint64_t km = 0, kp = nm;
+    for (uint64_t i = i0; i < i1; i++) {
+      const bool minus = a_minus && a_minus[i];
+      const uint64_t k = minus ? km++ : kp++;
+      ai[k] = minus ? 2 * slot[a[i]] : a[i];  // (the strings' offsets come in [start, end) pairs)
+      bi[k] = b[i];
+      out[k] = (uint32_t)(i - i0);
+      la[minus].push_back(length(a[i]));
+      lb[minus].push_back(length(b[i]));
+    }
+    if (nm) {
+      TRY(revseq_batch(c, uniq.data(), (uint32_t)uniq.size(), h_off));
+      a_off2.resize(2 * uniq.size());
+      for (size_t r = 0; r < uniq.size(); r++) {
+        a_off2[2 * r] = h_off[r];
+        a_off2[2 * r + 1] = h_off[r] + length(uniq[r]);
+        slot[uniq[r]] = NO_SLOT;
+      }
+      TRY(upload(c, c->s_j, a_off2.data(), a_off2.size(), c->stream));
+    }
+    TRY(upload(c, c->s_d, ai.data(), mb, c->stream));
+    TRY(upload(c, c->s_e, bi.data(), mb, c->stream));
+    TRY(upload(c, c->s_g, out.data(), mb, c->stream));
+    TRY(ensure(c->s_f, mb * 16 + 64));
+    double *d_id = (double *)c->s_f.p;
+    int32_t *d_len = (int32_t *)(d_id + mb), *d_ids = d_len + mb;
+    const uint32_t *d_ai = (const uint32_t *)c->s_d.p, *d_bi = (const uint32_t *)c->s_e.p, *d_out = (const uint32_t *)c->s_g.p;
+    if (nm)
+      TRY(launch_nw(c, (uint8_t *)c->rc_seq.p, (uint64_t *)c->s_j.p, d_ai, (uint8_t *)c->codes.p, (uint64_t *)c->seq_off.p, d_bi,
+                    nm, la[1], lb[1], d_id, d_len, d_ids, nullptr, d_out));
+    if (np)
+      TRY(launch_nw(c, (uint8_t *)c->codes.p, (uint64_t *)c->seq_off.p, d_ai + nm, (uint8_t *)c->codes.p,
+                    (uint64_t *)c->seq_off.p, d_bi + nm, np, la[0], lb[0], d_id, d_len, d_ids, nullptr, d_out + nm));
+    TRY(download_parts(c, {{ident ? ident + i0 : nullptr, d_id, mb * 8}, {len ? len + i0 : nullptr, d_len, mb * 4},
+                           {ids ? ids + i0 : nullptr, d_ids, mb * 4}}, c->stream));
+    i0 = i1;
+  }
   flush_timers(c);
   return MC_OK;
 }

@@ -160,6 +160,7 @@ struct mc_ctx {
   // scratch
   mcg::Buf s_a, s_b, s_c, s_d, s_e, s_f, s_g, s_h, s_i, s_j, s_k;
   mcg::Buf nw_items, nw_gran;  // NW chained row blocks: work items, bottom-row granules
+  mcg::Buf rc_seq;             // mc_nw_identity_strands / mc_revcomp_sequences: a batch's minus-strand strings
   // mc_update_iteration's member lists on the device and their host shadow: re-uploaded only
   // when a merge changed them (cleared when sequences are loaded: the ids were checked against n)
   mcg::Buf u_off, u_mem;
@@ -243,6 +244,10 @@ int launch_nw(mc_ctx *c, const uint8_t *d_A, const uint64_t *d_aoff, const uint3
               const uint64_t *d_boff, const uint32_t *d_bi, uint64_t m, const std::vector<uint64_t> &h_alen,
               const std::vector<uint64_t> &h_blen, double *d_ident, int32_t *d_len, int32_t *d_ids,
               int32_t *d_score, const uint32_t *d_out = nullptr);
+// revseq.hip: the minus-strand strings (host/revseq.hpp) of the u points d_ids into d_out at the
+// 16-byte-padded offsets d_out_off[u + 1] (out_bytes = its last entry); timed as F_LAYOUT
+int launch_revseq(mc_ctx *c, const uint32_t *d_ids, uint32_t u, const uint64_t *d_out_off, uint64_t out_bytes,
+                  uint8_t *d_out);
 
 }  // namespace mcg
 

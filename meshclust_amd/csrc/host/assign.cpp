@@ -16,16 +16,21 @@
 #include "fasta.hpp"
 #include "model.hpp"
 #include "topk.hpp"
+#include "verify.hpp"
 
 namespace mc {
 
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
-    "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--device N] [--threads N] [--stats-json FILE] "
-    "[--quiet]\n"
+    "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--device N] "
+    "[--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
     "  --top K --hits FILE  (given together, K = 1..8) also write the K best similar centres of every read to\n"
-    "                  FILE: read, rank, centre, cluster index, combo 0 (and the strand with --both-strands)\n";
+    "                  FILE: read, rank, centre, cluster index, combo 0 (and the strand with --both-strands)\n"
+    "  --identity      align every reported (read, centre) pair, the read reverse-complemented where it was\n"
+    "                  assigned on the minus strand; the TSV and the hits file gain a last column, the identity\n"
+    "  --min-identity X  (0 <= X <= 1, implies --identity) assign a read to the first of its hits (the --top K\n"
+    "                  best, or the best one) that aligns at identity X or more; none: the read is unassigned\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
   AssignOptions o;
@@ -48,7 +53,15 @@ AssignOptions parse_assign_options(int argc, char **argv) {
       if (o.top < 1 || o.top > MC_ASSIGN_MAX_TOP)
         throw Error(std::string("--top must be 1 .. ") + std::to_string(MC_ASSIGN_MAX_TOP) + "\n" + kUsage, 1);
     } else if (arg == "--hits" && has) o.hits = argv[++i];
-    else {
+    else if (arg == "--identity") o.identity = true;
+    else if (arg == "--min-identity" && has) {
+      char *end = nullptr;
+      const char *txt = argv[++i];
+      o.min_identity = strtod(txt, &end);
+      if (end == txt || *end || !(o.min_identity >= 0 && o.min_identity <= 1))
+        throw Error(std::string("--min-identity must be 0 .. 1\n") + kUsage, 1);
+      o.identity = true;
+    } else {
       struct stat st;
       if (stat(argv[i], &st) == 0 && S_ISREG(st.st_mode)) o.reads.push_back(argv[i]);
       else throw Error(std::string("unknown option or missing file: ") + argv[i] + "\n" + kUsage, 1);
@@ -224,9 +237,54 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   r.path = by_pairs ? "pairs" : "device";
   r.assign_ms = ms_since(t0);
   t0 = std::chrono::steady_clock::now();
+  // --identity: every reported (read, centre, strand) aligned in one call, the read as seq1 and
+  // reverse-complemented where the strand is minus.  A read's candidates are its hits (rank 1 is
+  // the TSV's row: aligned once), or its one assignment without --top.
+  const uint32_t Kc = K > 0 ? K : 1;
+  std::vector<double> cand_id;  // Kc slots per read, as hit / hit_val
+  std::vector<double> ident_q(M, -1.0);
+  if (opt.identity) {
+    r.identity = true;
+    const uint32_t *cj = K > 0 ? hit.data() : best.data();
+    const double *cv = K > 0 ? hit_val.data() : val.data();
+    const uint8_t *cs = K > 0 ? hit_strand.data() : opt.both_strands ? strand.data() : nullptr;
+    std::vector<uint32_t> pa, pb;
+    std::vector<uint8_t> pm;
+    std::vector<uint64_t> first(M + 1, 0);  // a read's candidates are pairs first[q] .. first[q + 1]
+    for (uint64_t q = 0; q < M; q++) {
+      for (uint32_t t = 0; t < Kc && cj[q * Kc + t] != MC_ASSIGN_NONE; t++) {
+        pa.push_back((uint32_t)(C + q));
+        pb.push_back(cj[q * Kc + t]);
+        pm.push_back(cs ? cs[q * Kc + t] : 0);
+        r.identity_cells += ds.lengths[C + q] * ds.lengths[cj[q * Kc + t]];
+      }
+      first[q + 1] = pa.size();
+    }
+    r.identity_pairs = pa.size();
+    std::vector<double> pid(pa.size(), 0.0);
+    check(mc_nw_identity_strands(ctx, pa.data(), pb.data(), pm.data(), pa.size(), pid.data(), nullptr, nullptr),
+          "mc_nw_identity_strands");
+    cand_id.assign((size_t)M * Kc, -1.0);
+    for (uint64_t q = 0; q < M; q++) {
+      const uint32_t n = (uint32_t)(first[q + 1] - first[q]);
+      std::copy(pid.begin() + first[q], pid.begin() + first[q + 1], cand_id.begin() + q * Kc);
+      int pick = n ? 0 : -1;
+      if (opt.min_identity >= 0) {  // the first candidate the alignment confirms (verify.hpp), or none
+        pick = verify_pick(&cand_id[q * Kc], n, opt.min_identity);
+        if (n && pick < 0) r.rejected++;
+        best[q] = pick < 0 ? MC_ASSIGN_NONE : cj[q * Kc + pick];
+        val[q] = pick < 0 ? -1.0 : cv[q * Kc + pick];
+        if (opt.both_strands) strand[q] = pick < 0 ? 0 : cs[q * Kc + pick];
+      }
+      if (pick >= 0) ident_q[q] = cand_id[q * Kc + pick];
+    }
+  }
+  r.identity_ms = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
   // one line per read, in input order: read header, centre header or *, cluster index or -1,
   // combo 0, similar centres (headers without their '>'); with both strands a sixth column: the
-  // strand the read was assigned on (+ or -), or * for an unassigned read
+  // strand the read was assigned on (+ or -), or * for an unassigned read; with --identity a last
+  // column: the identity of the row's alignment, or *
   std::string out;
   std::vector<uint32_t> rest;
   char num[64];
@@ -243,6 +301,10 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
       out += !has ? '*' : strand[q] ? '-' : '+';
       if (has && strand[q]) r.assigned_minus++;
     }
+    if (opt.identity) {  // the last column: the alignment identity of the row's pair, or *
+      if (has) snprintf(num, sizeof num, "\t%.17g", ident_q[q]);
+      out += has ? num : "\t*";
+    }
     out += '\n';
     if (has) r.assigned++;
     else rest.push_back((uint32_t)(C + q));
@@ -254,7 +316,8 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   if (!opt.unassigned.empty()) write_fasta(opt.unassigned, ds, rest.data(), rest.size());
   if (K > 0) {
     // one line per hit, reads in input order, ranks ascending: read header, rank (from 1), centre
-    // header, cluster index, combo 0; with both strands the hit's strand (+ or -)
+    // header, cluster index, combo 0; with both strands the hit's strand (+ or -); with --identity
+    // the identity of the hit's alignment
     out.clear();
     for (uint64_t q = 0; q < M; q++)
       for (uint32_t t = 0; t < K && hit[q * K + t] != MC_ASSIGN_NONE; t++) {
@@ -266,6 +329,10 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
         snprintf(num, sizeof num, "\t%u\t%.17g", j, hit_val[q * K + t]);
         out += num;
         if (opt.both_strands) out += hit_strand[q * K + t] ? "\t-" : "\t+";
+        if (opt.identity) {
+          snprintf(num, sizeof num, "\t%.17g", cand_id[q * K + t]);
+          out += num;
+        }
         out += '\n';
         r.hits++;
       }
@@ -279,19 +346,25 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
 }
 
 std::string assign_stats_json(const AssignResult &r) {
-  char b[896], s[192] = "";  // (one strand, no --top: exactly the keys there were before either option)
+  // (one strand, no --top, no --identity: exactly the keys there were before any of the options)
+  char b[1280], s[448] = "", idms[48] = "";
   int n = 0;
   if (r.strands != MC_STRAND_PLUS)
     n = snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
-  if (r.top > 0) snprintf(s + n, sizeof s - n, "\"top\": %d, \"hits\": %llu, ", r.top, (unsigned long long)r.hits);
+  if (r.top > 0) n += snprintf(s + n, sizeof s - n, "\"top\": %d, \"hits\": %llu, ", r.top, (unsigned long long)r.hits);
+  if (r.identity) {
+    snprintf(s + n, sizeof s - n, "\"identity_pairs\": %llu, \"identity_cells\": %llu, \"rejected\": %llu, ",
+             (unsigned long long)r.identity_pairs, (unsigned long long)r.identity_cells, (unsigned long long)r.rejected);
+    snprintf(idms, sizeof idms, "\"identity\": %.3f, ", r.identity_ms);
+  }
   snprintf(b, sizeof b,
            "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, %s\"k\": %d, \"width\": %d, "
            "\"path\": \"%s\", \"candidate_pairs\": %llu, \"fallback_pairs\": %llu, \"device_us\": %llu, "
-           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, \"write\": %.3f}}",
+           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f}}",
            (unsigned long long)r.reads, (unsigned long long)r.centres, (unsigned long long)r.assigned,
            (unsigned long long)(r.reads - r.assigned), s, r.k, r.width, r.path.c_str(), (unsigned long long)r.candidates,
            (unsigned long long)r.fallbacks, (unsigned long long)r.device_us, r.parse_ms, r.upload_ms, r.kmer_ms,
-           r.assign_ms, r.write_ms);
+           r.assign_ms, idms, r.write_ms);
   return b;
 }
 

@@ -17,6 +17,8 @@ struct AssignOptions {
   bool both_strands = false;  // --both-strands: score every read as written and reverse-complemented
   int top = 0;                // --top K (1..MC_ASSIGN_MAX_TOP) with --hits FILE: the K best centres per read
   std::string hits;
+  bool identity = false;      // --identity: align every reported (read, centre, strand), report the identity
+  double min_identity = -1;   // --min-identity X (0..1, implies identity; negative: off): verify.hpp
 };
 
 struct AssignResult {
@@ -29,8 +31,10 @@ struct AssignResult {
   uint64_t assigned_minus = 0;   // both strands: reads assigned on their reverse complement
   int top = 0;                   // --top: K, and the lines written to the hits file
   uint64_t hits = 0;
+  bool identity = false;         // --identity / --min-identity: pairs aligned, their cells (sum of len1 * len2),
+  uint64_t identity_pairs = 0, identity_cells = 0, rejected = 0;  // reads with a hit but none at >= X
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
-  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, write_ms = 0;
+  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0;
 };
 
 // Throws mc::Error (bad options: code 1 with the usage text in what()).
@@ -42,6 +46,11 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // With top / hits (mc_assign_top; on the pair list the same ordered insertion on the host) the
 // hits file gets one line per hit (read, rank, centre, cluster index, combo 0, and the strand
 // with both_strands); the TSV is the one written without them.
+// With identity (mc_nw_identity_strands, one call: every reported (read, centre, strand), the
+// read reverse-complemented where the strand is minus) the TSV and the hits file gain a last
+// column, the identity as %.17g or * for an unassigned read.  With min_identity >= 0 a read goes
+// to the first of its candidates (its hits; one without top) whose identity is at least that
+// (verify.hpp), else it is unassigned; n_similar and the hits file do not change.
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
 std::string assign_stats_json(const AssignResult &r);
 int assign_main(int argc, char **argv);

@@ -26,6 +26,16 @@ against a numpy reduction of the pair-list pass (every query's similar centres b
 descending, index ascending, cut at K) on the reads that pass covers; the both-strands lists
 against the merge, by the header's order, of the plus-alone and minus-alone lists.
 
+--identity also times the identity phase of meshclust-assign --identity: one mc_nw_identity_strands
+call over every (read, its centre) pair, with the reads on one strand (no minus pair) and with every
+second read taken on the minus strand (the call reverse-complements those reads on the device: the
+work of a file in which every second read is reverse-complemented; NW fills the whole matrix, so
+its cost does not depend on what is aligned).  The plus results are checked against mc_nw_identity,
+a sample of the minus results against mc_nw_identity_raw on strings reverse-complemented in numpy.
+Adds the call's wall time, the NW and reverse-complement kernel times (mc_timers), DP cells per
+second, the reverse-complement kernel's bytes per second against the measured HBM copy rate, and
+the ratio of the phase to the mc_assign call.
+
 Under rocprofv3 set MC_ACCUM_PLAIN_LAUNCH=1, as scripts/prof_round.sh does: the clustering's
 cooperative launch otherwise faults the profiler's exit handler, after the
 profile is written.
@@ -46,6 +56,7 @@ import bench  # noqa: E402  (the workload table and the FASTA cache)
 import meshclust_amd as M  # noqa: E402
 
 SIMDS, CLOCK_HZ = 256 * 4, 2.4e9  # MI355X: 256 CUs x 4 SIMDs, ~2.4 GHz
+HBM_COPY_BPS = 6.29e12  # MI355X: measured float4 copy rate (8.0 TB/s spec)
 
 
 def pairs_pass(eng, centres, queries, lens, sim, batch, top=None):
@@ -92,6 +103,55 @@ def pairs_pass(eng, centres, queries, lens, sim, batch, top=None):
     return best, val, nsim, cand, t_call
 
 
+def identity_phase(eng, ds, ptr, seq_off, lens, centres, queries, best, a, assign_us):
+    """Times mc_nw_identity_strands over every assigned read and its centre -> the keys for the line."""
+    has = best != M.ASSIGN_NONE
+    qa, cb = queries[has], centres[best[has]]
+    cells = int((lens[qa].astype(np.float64) * lens[cb].astype(np.float64)).sum())
+    codes = np.ctypeslib.as_array(M.C.cast(ptr[0], M.C.POINTER(M.C.c_uint8)), shape=(int(seq_off[-1]),))
+    out = {"identity_pairs": int(len(qa)), "identity_cells": cells}
+    plus = eng.nw_identity(qa, cb)
+    for name, am in (("one_strand", None), ("alternating", (np.arange(len(qa)) % 2).astype(np.uint8))):
+        wall, nw_ms, lay_ms = [], [], []
+        for r in range(a.warmup + a.rounds):
+            eng.timers(reset=True)
+            t0 = time.perf_counter()
+            got = eng.nw_identity_strands(qa, cb, am)
+            w = time.perf_counter() - t0
+            t = eng.timers()
+            if r >= a.warmup:
+                wall.append(w)
+                nw_ms.append(t["nw"][0])
+                lay_ms.append(t["layout"][0])
+        if am is None:
+            assert all(np.array_equal(x, y) for x, y in zip(got, plus)), "no minus pair differs from mc_nw_identity"
+        else:
+            assert all(np.array_equal(x[am == 0], y[am == 0]) for x, y in zip(got, plus)), "plus pairs differ from mc_nw_identity"
+            pick = np.flatnonzero(am)[:256]
+            rc = [(3 - codes[int(seq_off[i]):int(seq_off[i + 1])][::-1]).astype(np.uint8) for i in qa[pick]]  # (digits only)
+            cs = [codes[int(seq_off[j]):int(seq_off[j + 1])] for j in cb[pick]]
+            off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.uint64)  # noqa: E731
+            raw = eng.nw_identity_raw(np.concatenate(rc), off(rc), np.concatenate(cs), off(cs))
+            assert all(np.array_equal(x[pick], y) for x, y in zip(got, raw[:3])), "minus pairs differ from mc_nw_identity_raw"
+        w_s, n_ms, l_ms = float(np.median(wall)), float(np.median(nw_ms)), float(np.median(lay_ms))
+        out["identity_%s_call_wall_ms" % name] = round(1e3 * w_s, 3)
+        out["identity_%s_call_wall_ms_all" % name] = [round(1e3 * x, 3) for x in wall]
+        out["identity_%s_nw_device_ms" % name] = round(n_ms, 3)
+        out["identity_%s_cells_per_s" % name] = round(cells / (n_ms * 1e-3), 1)
+        out["identity_%s_over_mc_assign" % name] = round(1e3 * w_s / (assign_us * 1e-3), 1)
+        if am is not None:
+            ids = np.unique(qa[am != 0])
+            nbytes = int(lens[ids].sum()) + int(((lens[ids] + 15) // 16 * 16).sum())  # read once, written padded to 16
+            out["revseq_reads"] = int(len(ids))
+            out["revseq_bytes"] = nbytes
+            out["revseq_device_ms"] = round(l_ms, 4)
+            out["revseq_device_ms_all"] = [round(x, 4) for x in lay_ms]
+            out["revseq_bytes_per_s"] = round(nbytes / (l_ms * 1e-3), 1) if l_ms > 0 else None
+            out["revseq_share_of_hbm_copy_rate"] = round(nbytes / (l_ms * 1e-3) / HBM_COPY_BPS, 4) if l_ms > 0 else None
+    out["identity_outputs_equal"] = True
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=sorted(bench.WORKLOADS), default="B")
@@ -107,6 +167,9 @@ def main():
                     help="also time mc_assign_strands on both strands (the centres' permuted rows included)")
     ap.add_argument("--top", type=int, default=0, metavar="K",
                     help="also time mc_assign_top at K = 1, 4, 8 and K (plus alone; with --both-strands both strands too)")
+    ap.add_argument("--identity", action="store_true",
+                    help="also time the identity phase (mc_nw_identity_strands over every read and its centre), on one "
+                         "strand and with every second read on the minus strand")
     a = ap.parse_args()
     n, templates, seed = bench.WORKLOADS[a.workload]
     fasta = bench.ensure_fasta(n, 1000, templates, 0.03, seed)
@@ -263,6 +326,8 @@ def main():
             line[name + "_device_us_all"] = us
             line[name + "_over_assign_strands"] = round(float(np.median(us)) / base, 3)
         line["top_outputs_equal"] = True
+    if a.identity:
+        line.update(identity_phase(eng, ds, ptr, seq_off, lens, centres, queries, best, a, d_us))
     print(json.dumps(line))
     eng.close()
 
