@@ -323,6 +323,47 @@ int mc_nw_identity_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, co
                            double *ident, int32_t *len, int32_t *ids);
 
 /*
+ * THE ALIGNMENT of a pair is the chain of predecessor choices along which GlobAlignE's (path
+ * length, identities) payload reaches (la, lb): the reference keeps no path, but with its fixed
+ * tie rules (M before X before Y into M, M before the gap into a gap, the first maximum of M, X, Y
+ * at the end) that chain is one path, and its columns and '=' are the len and ids mc_nw_identity
+ * reports.  mc_nw_align_strands returns it for the pairs of mc_nw_identity_strands (the same
+ * operand rule: seq1 = point a[i], its minus-strand string where a_minus[i] != 0; seq2 = point
+ * b[i] as written; the distinct minus reads of a batch reverse-complemented once).
+ * Operations are words run << 4 | op with BAM's codes, in alignment order from the first column
+ * to the last: '=' and 'X' consume a base of each (state M), 'I' a base of seq1 alone (state X,
+ * lowerGap), 'D' a base of seq2 alone (state Y, upperGap).  Pair i's words are
+ * cigar[cig_off[i] .. cig_off[i + 1]); cig_off (m + 1, required) always receives the prefix sums
+ * of the counts.  cigar == NULL gives the offsets and score / len (columns) / ids ('=') only;
+ * cigar != NULL with cap < cig_off[m] is MC_ERR_ARG with cig_off valid and nothing written to
+ * cigar.  score, len and ids may be NULL.  An empty seq1 against lb bases is lb 'D' (and 0 words
+ * for two empty strings); the score is mc_nw_identity_raw's.
+ * Device: a forward pass records 4 bits per cell (a wavefront per pair, R = 4 / 8 / 16 rows per
+ * lane for la <= 256 / <= 512 / longer), ceil(la / (64 R)) * (lb + 63) * 32 R bytes per pair; a
+ * second kernel walks them back, a thread per pair, at most la + lb steps (a walk that has not
+ * reached the matrix's edge by then: MC_ERR_HIP).  The pairs are worked in batches: a batch ends at
+ * MC_ALIGN_BATCH_PAIRS pairs, before the pair that would take the choice words past
+ * MC_ALIGN_SCRATCH_BYTES, or where mc_nw_identity_strands' buffer of minus-strand strings would
+ * overflow; the context owns the scratch and reuses it.  A pair that alone needs more than the
+ * cap is MC_ERR_UNSUPPORTED, checked before any launch, no output written.  Environment, read per
+ * call: MC_ALIGN_BATCH=<pairs> and MC_ALIGN_SCRATCH=<bytes> lower the two caps.  Batching changes
+ * no result.  m = 0 is MC_OK, no sequences MC_ERR_STATE, an id >= n MC_ERR_ARG.  The forward and
+ * traceback kernels are timed as "nw", the reverse-complement kernel as "layout" (mc_timers).
+ * mc_nw_align_profile (a measurement aid): out[0], out[1] = device ms of the forward and of the
+ * traceback (+ packing) kernels, out[2] = choice bytes the batches held, since the last reset.
+ */
+#define MC_CIGAR_I 1u   /* consumes seq1 (the read) only  : state X / lowerGap */
+#define MC_CIGAR_D 2u   /* consumes seq2 (the centre) only: state Y / upperGap */
+#define MC_CIGAR_EQ 7u
+#define MC_CIGAR_X 8u   /* BAM's codes; word = run << 4 | op */
+#define MC_ALIGN_BATCH_PAIRS (1ull << 16)
+#define MC_ALIGN_SCRATCH_BYTES (1ull << 30)
+int mc_nw_align_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                        uint32_t *cigar, uint64_t cap, uint64_t *cig_off /* m + 1 */,
+                        int32_t *score, int32_t *len, int32_t *ids);
+int mc_nw_align_profile(mc_ctx *ctx, double *out /* 3 */, int reset);
+
+/*
  * Accumulation (ClusterFactory::accumulate, ClusterFactory.cpp:637-714).
  * The bvec of Runner.cpp:342-350 is only ever shrunk after insert_finalize, so the device
  * holds one static candidate order (bin-major, length-sorted within bins) plus an alive

@@ -31,6 +31,7 @@ ASSIGN_NONE = 0xFFFFFFFF
 MC_STRAND_PLUS, MC_STRAND_MINUS = 1, 2
 ASSIGN_MAX_TOP = 8  # MC_ASSIGN_MAX_TOP
 ERR_ARG, ERR_UNSUPPORTED = 1, 6
+CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # MC_CIGAR_*: mc_nw_align_strands' words are run << 4 | op
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
 
@@ -95,7 +96,8 @@ def gpu_lib():
                      "mc_mean_shift", "mc_update_iteration", "mc_timers", "mc_classify_values", "mc_mean_shift_select", "mc_accumulate",
                      "mc_scan_part", "mc_scan_commit", "mc_comm_unique_id", "mc_comm_create", "mc_comm_allgather",
                      "mc_comm_stats", "mc_comm_destroy", "mc_sync", "mc_assign", "mc_assign_strands",
-                     "mc_revcomp_rows", "mc_assign_top", "mc_revcomp_sequences", "mc_nw_identity_strands"):
+                     "mc_revcomp_rows", "mc_assign_top", "mc_revcomp_sequences", "mc_nw_identity_strands",
+                     "mc_nw_align_strands", "mc_nw_align_profile"):
             getattr(lib, name).restype = C.c_int
         lib.mc_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
         lib.mc_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -111,6 +113,9 @@ def gpu_lib():
         lib.mc_revcomp_sequences.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.mc_nw_identity_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
+        lib.mc_nw_align_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                            C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mc_nw_align_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _gpu = lib
     return _gpu
 
@@ -150,6 +155,10 @@ def host_lib():
         lib.mcl_assign_identity.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                             C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
                                             C.c_char_p, C.c_int]
+        lib.mcl_assign_paf.restype = C.c_int
+        lib.mcl_assign_paf.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                       C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
+                                       C.c_char_p, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -413,6 +422,40 @@ class Engine:
                                                _p(ids)), "mc_nw_identity_strands")
         return ident, ln, ids
 
+    def nw_align_strands(self, a, b, a_minus=None, cigar=True):
+        """mc_nw_align_strands: the alignments behind nw_identity_strands -> (cigar, cig_off, score,
+        len, ids).  ``cigar``: uint32 words run << 4 | op (CIGAR_I 1, CIGAR_D 2, CIGAR_EQ 7,
+        CIGAR_X 8), pair i's at cig_off[i] .. cig_off[i + 1], in alignment order; ``len`` the
+        alignment columns, ``ids`` the '=' columns.  ``cigar=False``: offsets and integers only
+        (cigar is None)."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        am = None if a_minus is None else np.ascontiguousarray(a_minus, np.uint8)
+        assert len(b) == len(a) and (am is None or len(am) == len(a))
+        m = len(a)
+        off = np.zeros(m + 1, np.uint64)
+        sc = np.zeros(m, np.int32)
+        ln = np.zeros(m, np.int32)
+        ids = np.zeros(m, np.int32)
+        if not cigar:
+            _check(self.lib.mc_nw_align_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), None, C.c_uint64(0), _p(off),
+                                                _p(sc), _p(ln), _p(ids)), "mc_nw_align_strands")
+            return None, off, sc, ln, ids
+        cap = 0  # a word per base at most: the lengths, from mc_revcomp_sequences' offsets (no device work)
+        for x in (a, b):
+            _check(self.lib.mc_revcomp_sequences(self.ctx, _p(x), m, None, _p(off)), "mc_revcomp_sequences")
+            cap += int(off[-1])
+        words = np.zeros(cap, np.uint32)
+        _check(self.lib.mc_nw_align_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), _p(words), C.c_uint64(cap), _p(off),
+                                            _p(sc), _p(ln), _p(ids)), "mc_nw_align_strands")
+        return words[:int(off[-1])], off, sc, ln, ids
+
+    def nw_align_profile(self, reset=False):
+        """mc_nw_align_profile -> (forward ms, traceback ms, choice bytes) since the last reset."""
+        out = np.zeros(3)
+        _check(self.lib.mc_nw_align_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_align_profile")
+        return float(out[0]), float(out[1]), float(out[2])
+
     def nw_identity_raw(self, a_cat, a_off, b_cat, b_off):
         a_cat = np.ascontiguousarray(a_cat, np.uint8)
         b_cat = np.ascontiguousarray(b_cat, np.uint8)
@@ -438,7 +481,7 @@ class Engine:
 
 
 def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None,
-                 identity=False, min_identity=None):
+                 identity=False, min_identity=None, paf=None):
     """Place the reads of the FASTA file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
@@ -454,13 +497,20 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     (mcl_assign_identity): every reported (read, centre, strand) is aligned, the TSV and the hits file
     gain a last column with the identity (* for an unassigned read); with ``min_identity`` a read goes
     to the first of its hits that aligns at that identity or more, else it is unassigned.  The stats
-    gain ``identity_pairs``, ``identity_cells``, ``rejected`` and the ``identity`` phase."""
+    gain ``identity_pairs``, ``identity_cells``, ``rejected`` and the ``identity`` phase.
+    ``paf``: meshclust-assign's --paf FILE (mcl_assign_paf; implies ``identity``): one PAF line with a
+    CIGAR (cg:Z:, = X I D) per aligned pair; the stats gain ``paf_pairs`` and ``cigar_ops``."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    if identity or min_identity is not None:
+    if paf is not None:
+        rc = lib.mcl_assign_paf(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
+                                hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),
+                                paf.encode(), buf, len(buf))
+    elif identity or min_identity is not None:
         rc = lib.mcl_assign_identity(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                      unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
                                      hits.encode() if hits else None, 1 if identity else 0,

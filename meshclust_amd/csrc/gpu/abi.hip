@@ -79,6 +79,10 @@ void flush_timers(mc_ctx *c) {
     (void)hipEventElapsedTime(&ms, c->ev_pool[pr.second], c->ev_pool[pr.second + 1]);
     c->fam_ms[pr.first] += ms;
     c->fam_n[pr.first] += 1;
+    if (pr.first >= F_NFAM) {  // the alignment kernels' own counters: part of "nw"
+      c->fam_ms[F_NW] += ms;
+      c->fam_n[F_NW] += 1;
+    }
   }
   c->ev_pending.clear();
 }
@@ -294,7 +298,8 @@ int mc_ctx_destroy(mc_ctx *c) {
                  &c->alive, &c->members, &c->member_keys, &c->partials, &c->scan_dev, &c->flags_out, &c->s_a, &c->s_b,
                  &c->s_c, &c->s_d, &c->s_e, &c->s_f, &c->s_g, &c->s_h, &c->s_i, &c->s_j, &c->s_k, &c->hs, &c->mag_s, &c->sumsq_s, &c->len_s, &c->ticket,
                  &c->msum, &c->ident_s, &c->al_a, &c->al_b, &c->al_out, &c->al_id, &c->ord_ids, &c->acc_out, &c->sp_words, &c->sp_keys,
-                 &c->sp_scr, &c->sp_nodes, &c->sp_nn, &c->sp_q, &c->sp_err, &c->u_off, &c->u_mem, &c->nw_items, &c->nw_gran, &c->rc_seq})
+                 &c->sp_scr, &c->sp_nodes, &c->sp_nn, &c->sp_q, &c->sp_err, &c->u_off, &c->u_mem, &c->nw_items, &c->nw_gran, &c->rc_seq, &c->tr_choice, &c->tr_bnd, &c->tr_ops, &c->tr_pairs, &c->tr_res, &c->tr_idx, &c->tr_dst,
+                 &c->tr_out, &c->tr_err})
     release(*b);
   if (c->h_scan) (void)hipHostFree(c->h_scan);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -901,6 +906,152 @@ int mc_nw_identity_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, cons
     i0 = i1;
   }
   flush_timers(c);
+  return MC_OK;
+}
+
+int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                        uint32_t *cigar, uint64_t cap, uint64_t *cig_off, int32_t *score, int32_t *len, int32_t *ids) {
+  if (!c || !c->codes.p) return MC_ERR_STATE;
+  if (!cig_off) return MC_ERR_ARG;
+  if (m == 0) {
+    cig_off[0] = 0;
+    return MC_OK;
+  }
+  if (!a || !b) return MC_ERR_ARG;
+  MCG_CHECK(hipSetDevice(c->device));
+  TRY(check_ids(c, a, m));
+  TRY(check_ids(c, b, m));
+  uint64_t pair_cap = MC_ALIGN_BATCH_PAIRS, scr_cap = MC_ALIGN_SCRATCH_BYTES;
+  if (const char *e = getenv("MC_ALIGN_BATCH")) {  // (read per call: the tests put batch ends inside small lists)
+    const long long v = atoll(e);
+    if (v > 0 && (uint64_t)v < pair_cap) pair_cap = (uint64_t)v;
+  }
+  if (const char *e = getenv("MC_ALIGN_SCRATCH")) {
+    const long long v = atoll(e);
+    if (v > 0 && (uint64_t)v < scr_cap) scr_cap = (uint64_t)v;
+  }
+  auto length = [&](uint32_t id) { return c->h_seq_off[id + 1] - c->h_seq_off[id]; };
+  for (uint64_t i = 0; i < m; i++) {  // before any launch, and before any output is written
+    const uint64_t la = length(a[i]), lb = length(b[i]);
+    if (la + lb >= (1ull << 27) || nw_trace_choice_bytes(la, lb) > scr_cap) {
+      set_error("mc_nw_align_strands: pair " + std::to_string(i) + " (" + std::to_string(la) + " x " + std::to_string(lb) +
+                ") needs " + std::to_string(nw_trace_choice_bytes(la, lb)) + " bytes of choices, the cap is " +
+                std::to_string(scr_cap));
+      return MC_ERR_UNSUPPORTED;
+    }
+  }
+  constexpr uint32_t NO_SLOT = 0xffffffffu;
+  std::vector<uint32_t> slot;  // point id -> its minus-strand string's slot in this batch's buffer
+  if (a_minus) slot.assign(c->n, NO_SLOT);
+  std::vector<uint32_t> uniq, words, nops(m);
+  std::vector<uint64_t> h_off, dst;
+  std::vector<TracePair> pairs;
+  std::vector<int32_t> res;
+  TRY(ensure(c->tr_err, 256));
+  for (uint64_t i0 = 0; i0 < m;) {
+    // the batch [i0, i1): ends at the pair cap, before the pair that would take the choice
+    // scratch past its cap, or where one more minus read's string would not fit (as
+    // mc_nw_identity_strands)
+    uniq.clear();
+    pairs.clear();
+    uint64_t i1 = i0, pad = 0, chb = 0, bnd = 0, opw = 0;
+    while (i1 < m && i1 - i0 < pair_cap) {
+      const uint64_t la = length(a[i1]), lb = length(b[i1]);
+      const uint64_t need = nw_trace_choice_bytes(la, lb);
+      if (i1 > i0 && chb + need > scr_cap) break;
+      const bool minus = a_minus && a_minus[i1];
+      if (minus && slot[a[i1]] == NO_SLOT) {
+        const uint64_t bytes = (la + 15) / 16 * 16;
+        if (!uniq.empty() && pad + bytes > MC_IDENT_BATCH_BYTES) break;
+        pad += bytes;
+        slot[a[i1]] = (uint32_t)uniq.size();
+        uniq.push_back(a[i1]);
+      }
+      TracePair pr;
+      pr.a_off = minus ? slot[a[i1]] : c->h_seq_off[a[i1]];  // (a minus pair: its slot, made an offset below)
+      pr.b_off = c->h_seq_off[b[i1]];
+      pr.ch_off = chb;
+      pr.bnd_off = bnd;
+      pr.ops_off = opw;
+      pr.la = (uint32_t)la;
+      pr.lb = (uint32_t)lb;
+      pr.a_rc = minus ? 1 : 0;
+      pr.r = (uint32_t)nw_trace_rows(la);
+      pairs.push_back(pr);
+      chb += need;
+      if (la > 64ull * pr.r) bnd += 3 * (lb + 1);
+      opw += la + lb;
+      i1++;
+    }
+    const uint64_t mb = i1 - i0;
+    if (!uniq.empty()) {
+      TRY(revseq_batch(c, uniq.data(), (uint32_t)uniq.size(), h_off));
+      for (TracePair &pr : pairs)
+        if (pr.a_rc) pr.a_off = h_off[pr.a_off];
+      for (uint32_t id : uniq) slot[id] = NO_SLOT;
+    }
+    TRY(ensure(c->tr_choice, chb + 64));
+    TRY(ensure(c->tr_bnd, bnd * 4 + 64));
+    TRY(ensure(c->tr_ops, opw * 4 + 64));
+    TRY(ensure(c->tr_res, mb * TRACE_RES * 4 + 64));
+    TRY(upload(c, c->tr_pairs, pairs.data(), mb, c->stream));
+    TRY(launch_nw_trace(c, pairs, (const TracePair *)c->tr_pairs.p, (const uint8_t *)c->rc_seq.p, (uint8_t *)c->tr_choice.p,
+                        (int *)c->tr_bnd.p, (uint32_t *)c->tr_ops.p, (int32_t *)c->tr_res.p, (int *)c->tr_err.p));
+    c->tr_choice_bytes += (double)chb;
+    res.resize(mb * TRACE_RES);
+    int herr = 0;
+    TRY(download_parts(c, {{res.data(), c->tr_res.p, mb * TRACE_RES * 4}, {&herr, c->tr_err.p, 4}}, c->stream));
+    if (herr) {
+      set_error("mc_nw_align_strands: a traceback did not reach the matrix's edge within la + lb steps");
+      return MC_ERR_HIP;
+    }
+    dst.resize(mb);
+    uint64_t tot = 0;
+    for (uint64_t k = 0; k < mb; k++) {
+      dst[k] = tot;
+      nops[i0 + k] = (uint32_t)res[k * TRACE_RES + 3];
+      tot += nops[i0 + k];
+      if (score) score[i0 + k] = res[k * TRACE_RES];
+      if (len) len[i0 + k] = res[k * TRACE_RES + 1];
+      if (ids) ids[i0 + k] = res[k * TRACE_RES + 2];
+    }
+    if (cigar && tot) {  // the batch's words, packed on the device, kept until the whole count is known
+      TRY(ensure(c->tr_out, tot * 4 + 64));
+      TRY(upload(c, c->tr_dst, dst.data(), mb, c->stream));
+      TRY(launch_nw_pack(c, (uint32_t)mb, (const TracePair *)c->tr_pairs.p, (const uint32_t *)c->tr_ops.p,
+                         (const int32_t *)c->tr_res.p, (const uint64_t *)c->tr_dst.p, (uint32_t *)c->tr_out.p));
+      const size_t at = words.size();
+      words.resize(at + tot);
+      MCG_CHECK(hipMemcpyAsync(words.data() + at, c->tr_out.p, tot * 4, hipMemcpyDeviceToHost, c->stream));
+      MCG_CHECK(hipStreamSynchronize(c->stream));
+    }
+    i0 = i1;
+  }
+  flush_timers(c);
+  cig_off[0] = 0;
+  for (uint64_t i = 0; i < m; i++) cig_off[i + 1] = cig_off[i] + nops[i];
+  if (cigar) {
+    if (cap < cig_off[m]) {
+      set_error("mc_nw_align_strands: cigar holds " + std::to_string(cap) + " words, the alignments have " +
+                std::to_string(cig_off[m]));
+      return MC_ERR_ARG;
+    }
+    if (!words.empty()) memcpy(cigar, words.data(), words.size() * 4);
+  }
+  return MC_OK;
+}
+
+int mc_nw_align_profile(mc_ctx *c, double *out, int reset) {
+  if (!c || !out) return MC_ERR_ARG;
+  (void)hipStreamSynchronize(c->stream);
+  flush_timers(c);
+  out[0] = c->fam_ms[F_NW_FWD];
+  out[1] = c->fam_ms[F_NW_TB];
+  out[2] = c->tr_choice_bytes;
+  if (reset) {
+    c->fam_ms[F_NW_FWD] = c->fam_ms[F_NW_TB] = c->fam_n[F_NW_FWD] = c->fam_n[F_NW_TB] = 0;
+    c->tr_choice_bytes = 0;
+  }
   return MC_OK;
 }
 

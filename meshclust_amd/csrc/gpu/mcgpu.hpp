@@ -28,7 +28,9 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 
 // Kernel families for the device timers (mc_timers): ms and launch count per family.
 // F_LAYOUT: the static bvec-order copies of the rows (build_static), after K1
-enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM };
+// F_NW_FWD / F_NW_TB: the forward and traceback kernels of nwtrace.hip; they count as F_NW in
+// mc_timers and are kept apart only for mc_nw_align_profile
+enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NALL };
 
 // Classifier in the form the kernels consume (mc_classifier + the exact decision threshold).
 struct DevClassifier {
@@ -83,6 +85,15 @@ struct Buf {
   void *p = nullptr;
   size_t bytes = 0;
 };
+
+// One pair of mc_nw_align_strands' batch (nwtrace.hip): seq1 at a_off of the minus-strand buffer
+// (a_rc) or of the loaded codes, seq2 at b_off of the codes; r rows per lane; where the pair's
+// choice words (bytes), boundary row (ints) and operation words (uint32, la + lb of them) start.
+struct TracePair {
+  uint64_t a_off, b_off, ch_off, bnd_off, ops_off;
+  uint32_t la, lb, a_rc, r;
+};
+constexpr int TRACE_RES = 5;  // per pair: score, columns, identities, operation words, final state
 
 // A range of one array of the device lazy introsort (split.hip): partitioned (left >= 0:
 // children left, left + 1, cut between them) or finished (fin: a sorted leaf).
@@ -161,6 +172,10 @@ struct mc_ctx {
   mcg::Buf s_a, s_b, s_c, s_d, s_e, s_f, s_g, s_h, s_i, s_j, s_k;
   mcg::Buf nw_items, nw_gran;  // NW chained row blocks: work items, bottom-row granules
   mcg::Buf rc_seq;             // mc_nw_identity_strands / mc_revcomp_sequences: a batch's minus-strand strings
+  // mc_nw_align_strands: a batch's choice words, boundary rows, operation words, pair records,
+  // results, launch lists, output offsets and packed operations; the error word
+  mcg::Buf tr_choice, tr_bnd, tr_ops, tr_pairs, tr_res, tr_idx, tr_dst, tr_out, tr_err;
+  double tr_choice_bytes = 0;  // choice bytes written since the last mc_nw_align_profile reset
   // mc_update_iteration's member lists on the device and their host shadow: re-uploaded only
   // when a merge changed them (cleared when sequences are loaded: the ids were checked against n)
   mcg::Buf u_off, u_mem;
@@ -172,8 +187,8 @@ struct mc_ctx {
   std::vector<hipEvent_t> ev_pool;
   std::vector<std::pair<int, int>> ev_pending;  // (family, pool index of the begin event)
   int ev_open = -1;
-  double fam_ms[mcg::F_NFAM] = {0};
-  double fam_n[mcg::F_NFAM] = {0};
+  double fam_ms[mcg::F_NALL] = {0};
+  double fam_n[mcg::F_NALL] = {0};
 };
 
 namespace mcg {
@@ -248,6 +263,16 @@ int launch_nw(mc_ctx *c, const uint8_t *d_A, const uint64_t *d_aoff, const uint3
 // 16-byte-padded offsets d_out_off[u + 1] (out_bytes = its last entry); timed as F_LAYOUT
 int launch_revseq(mc_ctx *c, const uint32_t *d_ids, uint32_t u, const uint64_t *d_out_off, uint64_t out_bytes,
                   uint8_t *d_out);
+
+// nwtrace.hip: rows per lane and choice bytes of a pair; the forward and traceback kernels over
+// a batch (results to d_res, TRACE_RES ints per pair; operation words to each pair's region of
+// d_ops; *d_err set by a walk that found no path); the copy of every pair's words to d_out[d_dst[p]]
+int nw_trace_rows(uint64_t la);
+uint64_t nw_trace_choice_bytes(uint64_t la, uint64_t lb);
+int launch_nw_trace(mc_ctx *c, const std::vector<TracePair> &h_pairs, const TracePair *d_pairs, const uint8_t *d_rc,
+                    uint8_t *d_choice, int *d_bnd, uint32_t *d_ops, int32_t *d_res, int *d_err);
+int launch_nw_pack(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint32_t *d_ops, const int32_t *d_res,
+                   const uint64_t *d_dst, uint32_t *d_out);
 
 }  // namespace mcg
 

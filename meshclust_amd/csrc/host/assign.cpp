@@ -13,6 +13,7 @@
 #include <omp.h>
 #endif
 
+#include "cigar.hpp"
 #include "fasta.hpp"
 #include "model.hpp"
 #include "topk.hpp"
@@ -22,7 +23,7 @@ namespace mc {
 
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
-    "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--device N] "
+    "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--device N] "
     "[--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
     "  --top K --hits FILE  (given together, K = 1..8) also write the K best similar centres of every read to\n"
@@ -30,7 +31,9 @@ static const char *kUsage =
     "  --identity      align every reported (read, centre) pair, the read reverse-complemented where it was\n"
     "                  assigned on the minus strand; the TSV and the hits file gain a last column, the identity\n"
     "  --min-identity X  (0 <= X <= 1, implies --identity) assign a read to the first of its hits (the --top K\n"
-    "                  best, or the best one) that aligns at identity X or more; none: the read is unassigned\n";
+    "                  best, or the best one) that aligns at identity X or more; none: the read is unassigned\n"
+    "  --paf FILE      (implies --identity) also write every aligned (read, centre) pair as a PAF line with its\n"
+    "                  CIGAR (cg:Z:, = X I D); on - the CIGAR runs along the reverse-complemented read\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
   AssignOptions o;
@@ -60,6 +63,9 @@ AssignOptions parse_assign_options(int argc, char **argv) {
       o.min_identity = strtod(txt, &end);
       if (end == txt || *end || !(o.min_identity >= 0 && o.min_identity <= 1))
         throw Error(std::string("--min-identity must be 0 .. 1\n") + kUsage, 1);
+      o.identity = true;
+    } else if (arg == "--paf" && has) {
+      o.paf = argv[++i];
       o.identity = true;
     } else {
       struct stat st;
@@ -262,8 +268,75 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
     }
     r.identity_pairs = pa.size();
     std::vector<double> pid(pa.size(), 0.0);
-    check(mc_nw_identity_strands(ctx, pa.data(), pb.data(), pm.data(), pa.size(), pid.data(), nullptr, nullptr),
-          "mc_nw_identity_strands");
+    if (opt.paf.empty()) {
+      check(mc_nw_identity_strands(ctx, pa.data(), pb.data(), pm.data(), pa.size(), pid.data(), nullptr, nullptr),
+            "mc_nw_identity_strands");
+    } else {
+      // --paf: the same pairs through mc_nw_align_strands, in chunks whose strings hold at most
+      // 2^26 bases together -- an upper bound on a chunk's operation words, so one buffer serves
+      // every chunk.  The identity is ids / len of that call, the division mc_nw_identity does.
+      r.paf = true;
+      const uint64_t kChunk = 1ull << 26;
+      std::vector<size_t> cut{0};  // chunk c is pairs cut[c] .. cut[c + 1]
+      uint64_t cap = 0, sum = 0;   // the largest chunk's bound (one pair may exceed 2^26 alone)
+      for (size_t p = 0; p < pa.size(); p++) {
+        const uint64_t w = ds.lengths[pa[p]] + ds.lengths[pb[p]];
+        if (p > cut.back() && sum + w > kChunk) {
+          cut.push_back(p);
+          sum = 0;
+        }
+        sum += w;
+        cap = std::max(cap, sum);
+      }
+      cut.push_back(pa.size());
+      FILE *pf = fopen(opt.paf.c_str(), "w");
+      if (!pf) throw Error("cannot write " + opt.paf + ": " + strerror(errno), 1);
+      struct Close {
+        FILE *&f;
+        ~Close() {
+          if (f) fclose(f);
+        }
+      } closer{pf};
+      std::vector<uint32_t> cig(cap);
+      std::vector<uint64_t> off;
+      std::vector<int32_t> sc, ln, idn;
+      std::string paf;
+      char num[96];
+      uint64_t q = 0;  // the read of the pair being written
+      for (size_t c = 0; c + 1 < cut.size(); c++) {
+        const size_t p0 = cut[c], n = cut[c + 1] - p0;
+        if (n == 0) continue;
+        off.assign(n + 1, 0);
+        sc.assign(n, 0);
+        ln.assign(n, 0);
+        idn.assign(n, 0);
+        check(mc_nw_align_strands(ctx, pa.data() + p0, pb.data() + p0, pm.data() + p0, n, cig.data(), cig.size(), off.data(),
+                                  sc.data(), ln.data(), idn.data()),
+              "mc_nw_align_strands");
+        paf.clear();
+        for (size_t k = 0; k < n; k++) {
+          const size_t p = p0 + k;
+          pid[p] = (double)idn[k] / (double)ln[k];
+          while (first[q + 1] <= p) q++;
+          const unsigned long long lq = ds.lengths[pa[p]], lc = ds.lengths[pb[p]];
+          paf.append(ds.headers[pa[p]].substr(1));
+          snprintf(num, sizeof num, "\t%llu\t0\t%llu\t%c\t", lq, lq, pm[p] ? '-' : '+');
+          paf += num;
+          paf.append(ds.headers[pb[p]].substr(1));
+          snprintf(num, sizeof num, "\t%llu\t0\t%llu\t%d\t%d\t255\tAS:i:%d\trk:i:%llu\tcg:Z:", lc, lc, idn[k], ln[k], sc[k],
+                   (unsigned long long)(p - first[q] + 1));
+          paf += num;
+          cigar_append(paf, cig.data() + off[k], off[k + 1] - off[k]);
+          paf += '\n';
+        }
+        if (fwrite(paf.data(), 1, paf.size(), pf) != paf.size()) throw Error("cannot write " + opt.paf, 1);
+        r.cigar_ops += off[n];
+      }
+      r.paf_pairs = pa.size();
+      FILE *done = pf;
+      pf = nullptr;
+      if (fclose(done) != 0) throw Error("cannot write " + opt.paf, 1);
+    }
     cand_id.assign((size_t)M * Kc, -1.0);
     for (uint64_t q = 0; q < M; q++) {
       const uint32_t n = (uint32_t)(first[q + 1] - first[q]);
@@ -353,8 +426,11 @@ std::string assign_stats_json(const AssignResult &r) {
     n = snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
   if (r.top > 0) n += snprintf(s + n, sizeof s - n, "\"top\": %d, \"hits\": %llu, ", r.top, (unsigned long long)r.hits);
   if (r.identity) {
-    snprintf(s + n, sizeof s - n, "\"identity_pairs\": %llu, \"identity_cells\": %llu, \"rejected\": %llu, ",
-             (unsigned long long)r.identity_pairs, (unsigned long long)r.identity_cells, (unsigned long long)r.rejected);
+    n += snprintf(s + n, sizeof s - n, "\"identity_pairs\": %llu, \"identity_cells\": %llu, \"rejected\": %llu, ",
+                  (unsigned long long)r.identity_pairs, (unsigned long long)r.identity_cells, (unsigned long long)r.rejected);
+    if (r.paf)
+      snprintf(s + n, sizeof s - n, "\"paf_pairs\": %llu, \"cigar_ops\": %llu, ", (unsigned long long)r.paf_pairs,
+               (unsigned long long)r.cigar_ops);
     snprintf(idms, sizeof idms, "\"identity\": %.3f, ", r.identity_ms);
   }
   snprintf(b, sizeof b,

@@ -19,6 +19,7 @@ struct AssignOptions {
   std::string hits;
   bool identity = false;      // --identity: align every reported (read, centre, strand), report the identity
   double min_identity = -1;   // --min-identity X (0..1, implies identity; negative: off): verify.hpp
+  std::string paf;            // --paf FILE (implies identity): the alignments of the reported pairs as PAF
 };
 
 struct AssignResult {
@@ -33,6 +34,8 @@ struct AssignResult {
   uint64_t hits = 0;
   bool identity = false;         // --identity / --min-identity: pairs aligned, their cells (sum of len1 * len2),
   uint64_t identity_pairs = 0, identity_cells = 0, rejected = 0;  // reads with a hit but none at >= X
+  bool paf = false;              // --paf: lines written, operation words of their CIGARs
+  uint64_t paf_pairs = 0, cigar_ops = 0;
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
   double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0;
 };
@@ -51,6 +54,12 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // column, the identity as %.17g or * for an unassigned read.  With min_identity >= 0 a read goes
 // to the first of its candidates (its hits; one without top) whose identity is at least that
 // (verify.hpp), else it is unassigned; n_similar and the hits file do not change.
+// With paf (implies identity) the same pairs go through mc_nw_align_strands instead, in chunks of
+// at most 2^26 bases of both strings together; the identity columns are its ids / len (the same
+// doubles), and the file gets one PAF line per aligned pair, reads in input order, ranks
+// ascending: read, its length, 0, its length, strand, centre, its length, 0, its length, ids, len,
+// 255, AS:i:score, rk:i:rank, cg:Z:CIGAR (cigar.hpp).  On '-' the CIGAR runs along the
+// reverse-complemented read.  min_identity selects as without paf; the PAF lists every aligned pair.
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
 std::string assign_stats_json(const AssignResult &r);
 int assign_main(int argc, char **argv);

@@ -36,6 +36,13 @@ Adds the call's wall time, the NW and reverse-complement kernel times (mc_timers
 second, the reverse-complement kernel's bytes per second against the measured HBM copy rate, and
 the ratio of the phase to the mc_assign call.
 
+--align also times mc_nw_align_strands (the alignments behind meshclust-assign --paf) over the same
+(read, its centre) pairs, every second read on the minus strand, with and without the operation
+words, against mc_nw_identity_strands on those pairs (that kernel is the baseline: it does not keep
+the path).  Adds the forward and the traceback kernels' device times (mc_nw_align_profile), the
+choice bytes the forward pass writes per second, DP cells per second and the ratios; len / ids are
+checked against mc_nw_identity_strands first.
+
 Under rocprofv3 set MC_ACCUM_PLAIN_LAUNCH=1, as scripts/prof_round.sh does: the clustering's
 cooperative launch otherwise faults the profiler's exit handler, after the
 profile is written.
@@ -152,6 +159,57 @@ def identity_phase(eng, ds, ptr, seq_off, lens, centres, queries, best, a, assig
     return out
 
 
+def align_phase(eng, lens, centres, queries, best, a):
+    """Times mc_nw_align_strands over every assigned read and its centre (every second read on the
+    minus strand) against mc_nw_identity_strands on the same pairs -> the keys for the line."""
+    has = best != M.ASSIGN_NONE
+    qa, cb = queries[has], centres[best[has]]
+    am = (np.arange(len(qa)) % 2).astype(np.uint8)
+    cells = int((lens[qa].astype(np.float64) * lens[cb].astype(np.float64)).sum())
+    out = {"align_pairs": int(len(qa)), "align_cells": cells}
+    res = {}
+    for name in ("identity", "align", "align_no_cigar"):
+        wall, nw_ms, fwd, tb, chb = [], [], [], [], []
+        for r in range(a.warmup + a.rounds):
+            eng.timers(reset=True)
+            eng.nw_align_profile(reset=True)
+            t0 = time.perf_counter()
+            if name == "identity":
+                got = eng.nw_identity_strands(qa, cb, am)
+            else:
+                got = eng.nw_align_strands(qa, cb, am, cigar=name == "align")
+            w = time.perf_counter() - t0
+            t, pr = eng.timers(), eng.nw_align_profile()
+            if r >= a.warmup:
+                wall.append(w)
+                nw_ms.append(t["nw"][0])
+                fwd.append(pr[0])
+                tb.append(pr[1])
+                chb.append(pr[2])
+        res[name] = got
+        out[name + "_call_wall_ms"] = round(1e3 * float(np.median(wall)), 3)
+        out[name + "_call_wall_ms_all"] = [round(1e3 * x, 3) for x in wall]
+        out[name + "_nw_device_ms"] = round(float(np.median(nw_ms)), 3)
+        if name != "identity":
+            f_ms, t_ms = float(np.median(fwd)), float(np.median(tb))
+            out[name + "_forward_device_ms"] = round(f_ms, 3)
+            out[name + "_forward_device_ms_all"] = [round(x, 3) for x in fwd]
+            out[name + "_traceback_device_ms"] = round(t_ms, 3)
+            out[name + "_traceback_device_ms_all"] = [round(x, 3) for x in tb]
+            out[name + "_choice_bytes"] = int(chb[-1])
+            out[name + "_choice_bytes_per_s"] = round(chb[-1] / (f_ms * 1e-3), 1) if f_ms > 0 else None
+            out[name + "_forward_cells_per_s"] = round(cells / (f_ms * 1e-3), 1) if f_ms > 0 else None
+            out[name + "_device_over_identity"] = round((f_ms + t_ms) / out["identity_nw_device_ms"], 3)
+            out[name + "_wall_over_identity"] = round(out[name + "_call_wall_ms"] / out["identity_call_wall_ms"], 3)
+    _, ln, ids = res["identity"]
+    words, off, _, a_ln, a_ids = res["align"]
+    assert np.array_equal(ln, a_ln) and np.array_equal(ids, a_ids), "len / ids differ from mc_nw_identity_strands"
+    assert np.array_equal(off, res["align_no_cigar"][1])
+    out["align_cigar_ops"] = int(off[-1])
+    out["align_outputs_equal"] = True
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=sorted(bench.WORKLOADS), default="B")
@@ -170,6 +228,10 @@ def main():
     ap.add_argument("--identity", action="store_true",
                     help="also time the identity phase (mc_nw_identity_strands over every read and its centre), on one "
                          "strand and with every second read on the minus strand")
+    ap.add_argument("--align", action="store_true",
+                    help="also time mc_nw_align_strands (the alignments behind --paf) over every read and its centre, every "
+                         "second read on the minus strand, against mc_nw_identity_strands on the same pairs: forward and "
+                         "traceback device time, choice bytes per second, and the ratios")
     a = ap.parse_args()
     n, templates, seed = bench.WORKLOADS[a.workload]
     fasta = bench.ensure_fasta(n, 1000, templates, 0.03, seed)
@@ -328,6 +390,8 @@ def main():
         line["top_outputs_equal"] = True
     if a.identity:
         line.update(identity_phase(eng, ds, ptr, seq_off, lens, centres, queries, best, a, d_us))
+    if a.align:
+        line.update(align_phase(eng, lens, centres, queries, best, a))
     print(json.dumps(line))
     eng.close()
 
