@@ -379,7 +379,12 @@ int mc_cluster_begin(mc_ctx *ctx, uint32_t first_id);
  * positions S..E (inclusive; the bvec_iterator range of ClusterFactory.cpp:650-654), then,
  * if some candidate was similar, bvec::remove_available (bvec.cpp:289-318) + get_mean
  * (ClusterFactory.cpp:382-425).  flagged_pos receives the removed static positions in
- * ascending (bvec) order; cap is its capacity.
+ * ascending (bvec) order; cap is its capacity.  cap < n_flagged is MC_ERR_ARG, and the step has
+ * then been applied in part: THE CONTEXT'S BVEC STATE (alive mask, cluster members) IS UNDEFINED
+ * after that error until the next mc_set_order.  A bad window (S > E, E >= n) or centre is
+ * MC_ERR_ARG with nothing changed.
+ * A step that flags nothing (is_min) leaves the cluster as it is, a new cluster included: further
+ * steps without an mc_cluster_begin in between go on growing the same cluster.
  */
 int mc_scan(mc_ctx *ctx, uint32_t centre_id, uint64_t S, uint64_t E, uint32_t *flagged_pos,
             uint64_t cap, mc_scan_result *res);

@@ -31,6 +31,7 @@ ASSIGN_NONE = 0xFFFFFFFF
 MC_STRAND_PLUS, MC_STRAND_MINUS = 1, 2
 ASSIGN_MAX_TOP = 8  # MC_ASSIGN_MAX_TOP
 ERR_ARG, ERR_UNSUPPORTED = 1, 6
+ERR_STATE = 3
 CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # MC_CIGAR_*: mc_nw_align_strands' words are run << 4 | op
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
@@ -116,8 +117,38 @@ def gpu_lib():
         lib.mc_nw_align_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                             C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mc_nw_align_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        _bind_steps(lib)
         _gpu = lib
     return _gpu
+
+
+def _bind_steps(lib):
+    """Argument types of the get_close / mean-shift step API, on any library with the C-ABI of
+    include/meshclust_amd.h."""
+    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+    lib.mc_set_order.argtypes = [vp, vp, u64]
+    lib.mc_kill.argtypes = [vp, u64]
+    lib.mc_cluster_begin.argtypes = [vp, u32]
+    lib.mc_scan.argtypes = [vp, u32, u64, u64, vp, u64, C.POINTER(ScanResult)]
+    lib.mc_scan_part.argtypes = [vp, u32, u64, u64, u32, u32, vp, u64, C.POINTER(ScanResult)]
+    lib.mc_scan_commit.argtypes = [vp, vp, u64, C.POINTER(ScanResult)]
+    lib.mc_align_part.argtypes = [vp, u32, u64, u64, u32, u32, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    lib.mc_scan_ident.argtypes = [vp, u32, u64, u64, vp, vp, u64, C.POINTER(ScanResult)]
+    lib.mc_mean_shift_range.argtypes = [vp, vp, u32, vp, vp, C.c_int, u32, u32, vp]
+    for name in ("mc_set_order", "mc_kill", "mc_cluster_begin", "mc_scan", "mc_scan_part", "mc_scan_commit",
+                 "mc_align_part", "mc_scan_ident", "mc_mean_shift_range", "mc_mean_shift"):
+        getattr(lib, name).restype = C.c_int
+    lib.mc_last_error.restype = C.c_char_p
+
+
+def load_engine_lib(path):
+    """Another library with libmcgpu's C-ABI (the tests' CPU oracle engine), for ``Engine(lib=...)``.
+    Loaded with ctypes' default RTLD_LOCAL: its mc_* names stay its own."""
+    lib = C.CDLL(path)
+    lib.mc_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.mc_ctx_destroy.argtypes = [C.c_void_p]
+    _bind_steps(lib)
+    return lib
 
 
 def host_lib():
@@ -169,23 +200,32 @@ def tune_host_heap():
     return bool(host_lib().mcl_tune_host_heap())
 
 
-def _check(rc, what):
+def _check(rc, what, lib=None):
     if rc != 0:
-        e = MCError("%s failed (%d): %s" % (what, rc, gpu_lib().mc_last_error().decode()))
+        e = MCError("%s failed (%d): %s" % (what, rc, (lib or gpu_lib()).mc_last_error().decode()))
         e.code = rc
         raise e
 
 
-class Engine:
-    """One libmcgpu context on one GPU (``mc_ctx``)."""
+def _scan_dict(r):
+    return {name: getattr(r, name) for name, _ in ScanResult._fields_}
 
-    def __init__(self, device=0):
-        self.lib = gpu_lib()
+
+class Engine:
+    """One libmcgpu context on one GPU (``mc_ctx``).  ``lib``: another library with the same C-ABI
+    (``load_engine_lib``) to drive instead of libmcgpu -- the loading, histogram, classifier and
+    step calls then go to it."""
+
+    def __init__(self, device=0, lib=None):
+        self.lib = lib if lib is not None else gpu_lib()
         self.ctx = C.c_void_p()
-        _check(self.lib.mc_ctx_create(device, C.byref(self.ctx)), "mc_ctx_create")
+        self._ck(self.lib.mc_ctx_create(device, C.byref(self.ctx)), "mc_ctx_create")
         self.n = 0
         self.width = 0
         self.B = 0
+
+    def _ck(self, rc, what):
+        _check(rc, what, self.lib)
 
     def close(self):
         if self.ctx:
@@ -206,7 +246,7 @@ class Engine:
         if seg.size == 0:
             seg = np.zeros(2, np.int32)
         self.n = len(seq_off) - 1
-        _check(self.lib.mc_load_sequences(self.ctx, _p(codes), _p(seq_off), C.c_uint64(self.n), _p(seg),
+        self._ck(self.lib.mc_load_sequences(self.ctx, _p(codes), _p(seq_off), C.c_uint64(self.n), _p(seg),
                                           _p(seg_off)), "mc_load_sequences")
 
     def load_packed(self, seqs, segs):
@@ -234,31 +274,31 @@ class Engine:
         ep = np.array(exc_pos, np.uint64)
         ev = np.array(exc_val, np.uint8)
         self.n = len(seqs)
-        _check(self.lib.mc_load_packed(self.ctx, _p(packed), _p(pk_off), _p(seq_off), C.c_uint64(self.n),
+        self._ck(self.lib.mc_load_packed(self.ctx, _p(packed), _p(pk_off), _p(seq_off), C.c_uint64(self.n),
                                        _p(ep) if len(ep) else None, _p(ev) if len(ev) else None, C.c_uint64(len(ep)),
                                        _p(seg), _p(seg_off)), "mc_load_packed")
 
     def kmer_max(self, k):
         out = C.c_uint64()
-        _check(self.lib.mc_kmer_max(self.ctx, k, C.byref(out)), "mc_kmer_max")
+        self._ck(self.lib.mc_kmer_max(self.ctx, k, C.byref(out)), "mc_kmer_max")
         return out.value
 
     def kmer_build(self, k, width):
-        _check(self.lib.mc_kmer_build(self.ctx, k, width), "mc_kmer_build")
+        self._ck(self.lib.mc_kmer_build(self.ctx, k, width), "mc_kmer_build")
         self.width, self.B = width, 4 ** k
 
     def histograms(self):
         dt = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[self.width]
         h = np.zeros((self.n, self.B), dt)
         m = np.zeros(self.n, np.uint64)
-        _check(self.lib.mc_get_histograms(self.ctx, _p(h), _p(m)), "mc_get_histograms")
+        self._ck(self.lib.mc_get_histograms(self.ctx, _p(h), _p(m)), "mc_get_histograms")
         return h, m
 
     def distance_keys(self, pivots, ids):
         pivots = np.ascontiguousarray(pivots, np.uint32)
         ids = np.ascontiguousarray(ids, np.uint32)
         keys = np.zeros((len(pivots), len(ids)), np.uint16)
-        _check(self.lib.mc_distance_keys(self.ctx, _p(pivots), C.c_uint32(len(pivots)), _p(ids),
+        self._ck(self.lib.mc_distance_keys(self.ctx, _p(pivots), C.c_uint32(len(pivots)), _p(ids),
                                          C.c_uint64(len(ids)), _p(keys)), "mc_distance_keys")
         return keys
 
@@ -267,12 +307,12 @@ class Engine:
         b = np.ascontiguousarray(b, np.uint32)
         fl = np.ascontiguousarray(flags, np.uint16)
         raw = np.zeros((len(a), len(fl)), np.float64)
-        _check(self.lib.mc_pair_features(self.ctx, _p(a), _p(b), C.c_uint64(len(a)), _p(fl), len(fl), _p(raw)),
+        self._ck(self.lib.mc_pair_features(self.ctx, _p(a), _p(b), C.c_uint64(len(a)), _p(fl), len(fl), _p(raw)),
                "mc_pair_features")
         return raw
 
     def set_classifier(self, cls):
-        _check(self.lib.mc_set_classifier(self.ctx, C.byref(cls)), "mc_set_classifier")
+        self._ck(self.lib.mc_set_classifier(self.ctx, C.byref(cls)), "mc_set_classifier")
 
     def classify_pairs(self, a, b):
         a = np.ascontiguousarray(a, np.uint32)
@@ -280,7 +320,7 @@ class Engine:
         sim = np.zeros(len(a), np.uint8)
         c0 = np.zeros(len(a))
         s = np.zeros(len(a))
-        _check(self.lib.mc_classify_pairs(self.ctx, _p(a), _p(b), C.c_uint64(len(a)), _p(sim), _p(c0), _p(s)),
+        self._ck(self.lib.mc_classify_pairs(self.ctx, _p(a), _p(b), C.c_uint64(len(a)), _p(sim), _p(c0), _p(s)),
                "mc_classify_pairs")
         return sim, c0, s
 
@@ -295,7 +335,7 @@ class Engine:
         val = np.full(m, -1.0)
         nsim = np.zeros(m, np.uint32)
         stats = np.zeros(3, np.uint64)
-        _check(self.lib.mc_assign(self.ctx, _p(centres), len(centres), _p(queries), m, float(sim), _p(best), _p(val),
+        self._ck(self.lib.mc_assign(self.ctx, _p(centres), len(centres), _p(queries), m, float(sim), _p(best), _p(val),
                                   _p(nsim), _p(stats)), "mc_assign")
         return best, val, nsim, stats
 
@@ -311,7 +351,7 @@ class Engine:
         strand = np.zeros(m, np.uint8)
         nsim = np.zeros(m, np.uint32)
         stats = np.zeros(3, np.uint64)
-        _check(self.lib.mc_assign_strands(self.ctx, _p(centres), len(centres), _p(queries), m, float(sim), int(strands),
+        self._ck(self.lib.mc_assign_strands(self.ctx, _p(centres), len(centres), _p(queries), m, float(sim), int(strands),
                                           _p(best), _p(val), _p(strand), _p(nsim), _p(stats)), "mc_assign_strands")
         return best, val, strand, nsim, stats
 
@@ -328,7 +368,7 @@ class Engine:
         strand = np.zeros((m, kk), np.uint8)
         nsim = np.zeros(m, np.uint32)
         stats = np.zeros(3, np.uint64)
-        _check(self.lib.mc_assign_top(self.ctx, _p(centres), len(centres), _p(queries), m, float(sim), int(strands), int(k),
+        self._ck(self.lib.mc_assign_top(self.ctx, _p(centres), len(centres), _p(queries), m, float(sim), int(strands), int(k),
                                       _p(hit), _p(val), _p(strand), _p(nsim), _p(stats)), "mc_assign_top")
         return hit, val, strand, nsim, stats
 
@@ -338,7 +378,7 @@ class Engine:
         ids = np.ascontiguousarray(ids, np.uint32)
         dt = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[self.width]
         rows = np.zeros((len(ids), self.B), dt)
-        _check(self.lib.mc_revcomp_rows(self.ctx, _p(ids), len(ids), _p(rows)), "mc_revcomp_rows")
+        self._ck(self.lib.mc_revcomp_rows(self.ctx, _p(ids), len(ids), _p(rows)), "mc_revcomp_rows")
         return rows
 
     def classify_values(self, raw):
@@ -348,7 +388,7 @@ class Engine:
         sim = np.zeros(m, np.uint8)
         c0 = np.zeros(m)
         s = np.zeros(m)
-        _check(self.lib.mc_classify_values(self.ctx, _p(raw), C.c_uint64(m), _p(sim), _p(c0), _p(s)),
+        self._ck(self.lib.mc_classify_values(self.ctx, _p(raw), C.c_uint64(m), _p(sim), _p(c0), _p(s)),
                "mc_classify_values")
         return sim, c0, s
 
@@ -357,7 +397,7 @@ class Engine:
         member_off = np.ascontiguousarray(member_off, np.uint64)
         members = np.ascontiguousarray(members, np.uint32)
         out = np.zeros(len(centres), np.uint32)
-        _check(self.lib.mc_mean_shift(self.ctx, _p(centres), len(centres), _p(member_off), _p(members), delta, _p(out)),
+        self._ck(self.lib.mc_mean_shift(self.ctx, _p(centres), len(centres), _p(member_off), _p(members), delta, _p(out)),
                "mc_mean_shift")
         return out
 
@@ -372,10 +412,78 @@ class Engine:
         sim = np.zeros(max(m, 1), np.uint8)
         c0 = np.zeros(max(m, 1))
         n = C.c_uint64(0)
-        _check(self.lib.mc_update_iteration(self.ctx, _p(centres), C_, _p(member_off), _p(members), delta, _p(out),
+        self._ck(self.lib.mc_update_iteration(self.ctx, _p(centres), C_, _p(member_off), _p(members), delta, _p(out),
                                             _p(sim), _p(c0), C.byref(n)), "mc_update_iteration")
         assert n.value == m
         return out, sim[:m], c0[:m]
+
+    # ---- the step API: every call returns its return code first (nothing raises), so a driver
+    # can run the same script on two engines and compare the codes as well
+    def set_order(self, order):
+        """mc_set_order: order[pos] = point id, a permutation of all points -> rc."""
+        order = np.ascontiguousarray(order, np.uint32)
+        return self.lib.mc_set_order(self.ctx, _p(order), len(order))
+
+    def kill(self, pos):
+        """mc_kill of one static position -> rc."""
+        return self.lib.mc_kill(self.ctx, int(pos))
+
+    def cluster_begin(self, first):
+        """mc_cluster_begin: the next step starts the cluster {first} -> rc."""
+        return self.lib.mc_cluster_begin(self.ctx, int(first))
+
+    def scan(self, centre, S, E, cap=None):
+        """mc_scan -> (rc, result dict of the mc_scan_result fields, flagged positions).  ``cap``:
+        capacity of the flagged buffer (default: the window)."""
+        cap = max(int(E) - int(S) + 1, 1) if cap is None else int(cap)
+        fl = np.zeros(max(cap, 1), np.uint32)
+        r = ScanResult()
+        rc = self.lib.mc_scan(self.ctx, int(centre), int(S), int(E), _p(fl), cap, C.byref(r))
+        return rc, _scan_dict(r), fl[:min(int(r.n_flagged), cap)].copy() if rc == 0 else fl[:0]
+
+    def scan_part(self, centre, S, E, part, nparts, cap=None):
+        """mc_scan_part -> (rc, result dict, this part's similar positions)."""
+        cap = max(int(E) - int(S) + 1, 1) if cap is None else int(cap)
+        fl = np.zeros(max(cap, 1), np.uint32)
+        r = ScanResult()
+        rc = self.lib.mc_scan_part(self.ctx, int(centre), int(S), int(E), int(part), int(nparts), _p(fl), cap, C.byref(r))
+        return rc, _scan_dict(r), fl[:min(int(r.n_flagged), cap)].copy() if rc == 0 else fl[:0]
+
+    def scan_commit(self, flagged):
+        """mc_scan_commit of the merged (ascending) positions -> (rc, result dict)."""
+        fl = np.ascontiguousarray(flagged, np.uint32)
+        r = ScanResult()
+        rc = self.lib.mc_scan_commit(self.ctx, _p(fl) if len(fl) else None, len(fl), C.byref(r))
+        return rc, _scan_dict(r)
+
+    def align_part(self, centre, S, E, part, nparts, cap=None):
+        """mc_align_part -> (rc, this part's identities, pairs, cells of the whole window)."""
+        cap = max(int(E) - int(S) + 1, 1) if cap is None else int(cap)
+        ident = np.zeros(max(cap, 1))
+        n, pairs, cells = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.mc_align_part(self.ctx, int(centre), int(S), int(E), int(part), int(nparts), _p(ident), cap,
+                                    C.byref(n), C.byref(pairs), C.byref(cells))
+        return rc, ident[:min(n.value, cap)].copy() if rc == 0 else ident[:0], pairs.value, cells.value
+
+    def scan_ident(self, centre, S, E, ident, cap=None):
+        """mc_scan_ident: mc_scan's alignment-mode step with the window's identities given ->
+        (rc, result dict, flagged positions)."""
+        cap = max(int(E) - int(S) + 1, 1) if cap is None else int(cap)
+        ident = np.ascontiguousarray(ident, np.float64)
+        fl = np.zeros(max(cap, 1), np.uint32)
+        r = ScanResult()
+        rc = self.lib.mc_scan_ident(self.ctx, int(centre), int(S), int(E), _p(ident), _p(fl), cap, C.byref(r))
+        return rc, _scan_dict(r), fl[:min(int(r.n_flagged), cap)].copy() if rc == 0 else fl[:0]
+
+    def mean_shift_range(self, centres, member_off, members, delta, j0, j1):
+        """mc_mean_shift_range: the new centres of j0 <= j < j1 -> (rc, new centres)."""
+        centres = np.ascontiguousarray(centres, np.uint32)
+        member_off = np.ascontiguousarray(member_off, np.uint64)
+        members = np.ascontiguousarray(members, np.uint32)
+        out = np.zeros(max(int(j1) - int(j0), 1), np.uint32)
+        rc = self.lib.mc_mean_shift_range(self.ctx, _p(centres), len(centres), _p(member_off), _p(members), int(delta),
+                                          int(j0), int(j1), _p(out))
+        return rc, out[:max(int(j1) - int(j0), 0)]
 
     def mean_shift_select(self, centres, member_off, members, delta, keep):
         centres = np.ascontiguousarray(centres, np.uint32)
@@ -383,7 +491,7 @@ class Engine:
         members = np.ascontiguousarray(members, np.uint32)
         keep = np.ascontiguousarray(keep, np.uint8)
         out = np.zeros(len(centres), np.uint32)
-        _check(self.lib.mc_mean_shift_select(self.ctx, _p(centres), len(centres), _p(member_off), _p(members), delta,
+        self._ck(self.lib.mc_mean_shift_select(self.ctx, _p(centres), len(centres), _p(member_off), _p(members), delta,
                                              _p(keep), _p(out)), "mc_mean_shift_select")
         return out
 
@@ -393,7 +501,7 @@ class Engine:
         ident = np.zeros(len(a))
         ln = np.zeros(len(a), np.int32)
         ids = np.zeros(len(a), np.int32)
-        _check(self.lib.mc_nw_identity(self.ctx, _p(a), _p(b), C.c_uint64(len(a)), _p(ident), _p(ln), _p(ids)),
+        self._ck(self.lib.mc_nw_identity(self.ctx, _p(a), _p(b), C.c_uint64(len(a)), _p(ident), _p(ln), _p(ids)),
                "mc_nw_identity")
         return ident, ln, ids
 
@@ -403,9 +511,9 @@ class Engine:
         -> (bytes uint8, off uint64 of len(ids) + 1)."""
         ids = np.ascontiguousarray(ids, np.uint32)
         off = np.zeros(len(ids) + 1, np.uint64)
-        _check(self.lib.mc_revcomp_sequences(self.ctx, _p(ids), len(ids), None, _p(off)), "mc_revcomp_sequences")
+        self._ck(self.lib.mc_revcomp_sequences(self.ctx, _p(ids), len(ids), None, _p(off)), "mc_revcomp_sequences")
         out = np.zeros(int(off[-1]), np.uint8)
-        _check(self.lib.mc_revcomp_sequences(self.ctx, _p(ids), len(ids), _p(out), _p(off)), "mc_revcomp_sequences")
+        self._ck(self.lib.mc_revcomp_sequences(self.ctx, _p(ids), len(ids), _p(out), _p(off)), "mc_revcomp_sequences")
         return out, off
 
     def nw_identity_strands(self, a, b, a_minus=None):
@@ -418,7 +526,7 @@ class Engine:
         ident = np.zeros(len(a))
         ln = np.zeros(len(a), np.int32)
         ids = np.zeros(len(a), np.int32)
-        _check(self.lib.mc_nw_identity_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(len(a)), _p(ident), _p(ln),
+        self._ck(self.lib.mc_nw_identity_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(len(a)), _p(ident), _p(ln),
                                                _p(ids)), "mc_nw_identity_strands")
         return ident, ln, ids
 
@@ -438,22 +546,22 @@ class Engine:
         ln = np.zeros(m, np.int32)
         ids = np.zeros(m, np.int32)
         if not cigar:
-            _check(self.lib.mc_nw_align_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), None, C.c_uint64(0), _p(off),
+            self._ck(self.lib.mc_nw_align_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), None, C.c_uint64(0), _p(off),
                                                 _p(sc), _p(ln), _p(ids)), "mc_nw_align_strands")
             return None, off, sc, ln, ids
         cap = 0  # a word per base at most: the lengths, from mc_revcomp_sequences' offsets (no device work)
         for x in (a, b):
-            _check(self.lib.mc_revcomp_sequences(self.ctx, _p(x), m, None, _p(off)), "mc_revcomp_sequences")
+            self._ck(self.lib.mc_revcomp_sequences(self.ctx, _p(x), m, None, _p(off)), "mc_revcomp_sequences")
             cap += int(off[-1])
         words = np.zeros(cap, np.uint32)
-        _check(self.lib.mc_nw_align_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), _p(words), C.c_uint64(cap), _p(off),
+        self._ck(self.lib.mc_nw_align_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), _p(words), C.c_uint64(cap), _p(off),
                                             _p(sc), _p(ln), _p(ids)), "mc_nw_align_strands")
         return words[:int(off[-1])], off, sc, ln, ids
 
     def nw_align_profile(self, reset=False):
         """mc_nw_align_profile -> (forward ms, traceback ms, choice bytes) since the last reset."""
         out = np.zeros(3)
-        _check(self.lib.mc_nw_align_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_align_profile")
+        self._ck(self.lib.mc_nw_align_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_align_profile")
         return float(out[0]), float(out[1]), float(out[2])
 
     def nw_identity_raw(self, a_cat, a_off, b_cat, b_off):
@@ -466,17 +574,17 @@ class Engine:
         ln = np.zeros(m, np.int32)
         ids = np.zeros(m, np.int32)
         sc = np.zeros(m, np.int32)
-        _check(self.lib.mc_nw_identity_raw(self.ctx, _p(a_cat), _p(a_off), _p(b_cat), _p(b_off), C.c_uint64(m),
+        self._ck(self.lib.mc_nw_identity_raw(self.ctx, _p(a_cat), _p(a_off), _p(b_cat), _p(b_off), C.c_uint64(m),
                                            _p(ident), _p(ln), _p(ids), _p(sc)), "mc_nw_identity_raw")
         return ident, ln, ids, sc
 
     def sync(self):
         """Wait for all work on this context's GPU (mc_sync)."""
-        _check(self.lib.mc_sync(self.ctx), "mc_sync")
+        self._ck(self.lib.mc_sync(self.ctx), "mc_sync")
 
     def timers(self, reset=False):
         out = np.zeros(2 * len(FAMILIES))
-        _check(self.lib.mc_timers(self.ctx, _p(out), len(out), 1 if reset else 0), "mc_timers")
+        self._ck(self.lib.mc_timers(self.ctx, _p(out), len(out), 1 if reset else 0), "mc_timers")
         return {f: (out[2 * i], int(out[2 * i + 1])) for i, f in enumerate(FAMILIES)}
 
 

@@ -249,15 +249,21 @@ __global__ __launch_bounds__(ST) void fused_scan_kernel(FusedArgs A, DevClassifi
   __syncthreads();
   STAMP(3);
   const uint32_t nflag = __hip_atomic_load(&A.sd->nflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const uint32_t M = A.part ? A.sd->nmembers : mbase + nflag;
+  const uint32_t M = A.part ? mbase : mbase + nflag;  // (a part of a new cluster's first step: {first})
   uint32_t new_id = 0xffffffffu;
-  if (nflag > 0 && !A.part) {
-    if (A.new_cluster) {
-      if (threadIdx.x == 0) {
-        A.mem_pos[0] = (uint32_t)A.first_pos;
-        A.mkeys[0] = 0;
-      }
+  if (A.new_cluster && !A.part) {
+    if (threadIdx.x == 0) {
+      A.mem_pos[0] = (uint32_t)A.first_pos;
+      A.mkeys[0] = 0;
     }
+    // a new cluster's step that flags nothing still starts the cluster: a later step of the same
+    // cluster (no mc_cluster_begin in between) folds its rows into these sums
+    if (nflag == 0) {
+      const RowRef R{A.hs, 1, A.npad};
+      for (int b = threadIdx.x; b < A.B; b += ST) A.msum[b] = elem<T>(R, A.first_pos, b);
+    }
+  }
+  if (nflag > 0 && !A.part) {
     const RowRef R{A.hs, 1, A.npad};
     // integer column sums of the cluster: running sum from the previous step (or the new
     // cluster's first member) + this step's flagged members, folded in LDS
@@ -323,6 +329,10 @@ __global__ __launch_bounds__(ST) void commit_kernel(CommitArgs A) {
   }
   __syncthreads();
   uint32_t new_id = 0xffffffffu;
+  if (A.new_cluster && A.nflag == 0) {  // the cluster starts here all the same (see fused_scan_kernel)
+    const RowRef R{A.hs, 1, A.npad};
+    for (int b = threadIdx.x; b < A.B; b += ST) A.msum[b] = elem<T>(R, A.first_pos, b);
+  }
   if (A.nflag > 0) {  // the same running integer sums + closest member as fused_scan_kernel
     const RowRef R{A.hs, 1, A.npad};
     uint64_t *lsum;

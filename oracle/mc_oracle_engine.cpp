@@ -292,10 +292,12 @@ int mc_set_order(mc_ctx *c, const uint32_t *order, uint64_t n) {
   return MC_OK;
 }
 int mc_kill(mc_ctx *c, uint64_t pos) {
+  if (pos >= c->order.size()) return fail(MC_ERR_ARG, "mc_kill: position out of range");
   c->alive[pos] = 0;
   return MC_OK;
 }
 int mc_cluster_begin(mc_ctx *c, uint32_t first) {
+  if (first >= c->n || c->order.empty()) return fail(MC_ERR_ARG, "mc_cluster_begin: bad first member");
   c->members.assign(1, first);
   return MC_OK;
 }
@@ -371,12 +373,14 @@ static int scan_loop(mc_ctx *c, uint32_t centre, uint64_t S, uint64_t E, const s
   res->best_pos = best_pos;
   res->best_val = best_val;
   res->n_flagged = nf;
-  if (!is_min) res->new_centre = mean_closest(c, c->members);
+  res->new_centre = is_min ? 0xffffffffu : mean_closest(c, c->members);
   res->n_members = (uint32_t)c->members.size();
   return MC_OK;
 }
 
 int mc_scan(mc_ctx *c, uint32_t centre, uint64_t S, uint64_t E, uint32_t *flagged, uint64_t cap, mc_scan_result *res) {
+  if (!res || !c->has_cls || c->order.empty()) return fail(MC_ERR_STATE, "mc_scan: no classifier or no order");
+  if (S > E || E >= c->order.size() || centre >= c->n) return fail(MC_ERR_ARG, "bad window");
   std::vector<double> ident;
   if (c->align) {  // Feature::align(*pt, *p) for the whole window, then the serial loop
     ident.assign(E - S + 1, 0.0);
@@ -412,7 +416,7 @@ int mc_align_part(mc_ctx *c, uint32_t centre, uint64_t S, uint64_t E, uint32_t p
 int mc_scan_ident(mc_ctx *c, uint32_t centre, uint64_t S, uint64_t E, const double *ident, uint32_t *flagged,
                   uint64_t cap, mc_scan_result *res) {
   if (!c->align) return fail(MC_ERR_STATE, "mc_scan_ident: alignment mode only");
-  if (S > E || E >= c->order.size()) return fail(MC_ERR_ARG, "bad window");
+  if (S > E || E >= c->order.size() || centre >= c->n) return fail(MC_ERR_ARG, "bad window");
   std::vector<double> win(E - S + 1, 0.0);
   uint64_t i = 0;
   for (uint64_t pos = S; pos <= E; pos++)
@@ -423,7 +427,8 @@ int mc_scan_ident(mc_ctx *c, uint32_t centre, uint64_t S, uint64_t E, const doub
 int mc_scan_part(mc_ctx *c, uint32_t centre, uint64_t S, uint64_t E, uint32_t part, uint32_t nparts, uint32_t *flagged,
                  uint64_t cap, mc_scan_result *res) {
   if (c->align) return fail(MC_ERR_UNSUPPORTED, "sharded get_close steps take k-mer histograms");
-  if (S > E || E >= c->order.size() || nparts == 0 || part >= nparts) return fail(MC_ERR_ARG, "bad sharded window");
+  if (S > E || E >= c->order.size() || centre >= c->n || nparts == 0 || part >= nparts)
+    return fail(MC_ERR_ARG, "bad sharded window");
   memset(res, 0, sizeof *res);
   double best_val = -1;
   bool has = false;
@@ -454,10 +459,12 @@ int mc_scan_part(mc_ctx *c, uint32_t centre, uint64_t S, uint64_t E, uint32_t pa
 
 int mc_scan_commit(mc_ctx *c, const uint32_t *flagged, uint64_t n, mc_scan_result *res) {
   if (c->align) return fail(MC_ERR_UNSUPPORTED, "sharded get_close steps take k-mer histograms");
-  memset(res, 0, sizeof *res);
-  for (uint64_t i = 0; i < n; i++) {
+  if (n > c->order.size() || (n && !flagged)) return fail(MC_ERR_ARG, "mc_scan_commit: bad list");
+  for (uint64_t i = 0; i < n; i++)  // checked before anything is applied: an error leaves the state alone
     if (flagged[i] >= c->order.size() || !c->alive[flagged[i]] || (i && flagged[i] <= flagged[i - 1]))
       return fail(MC_ERR_ARG, "mc_scan_commit: positions must be ascending, alive and in range");
+  memset(res, 0, sizeof *res);
+  for (uint64_t i = 0; i < n; i++) {
     c->alive[flagged[i]] = 0;
     c->members.push_back(c->order[flagged[i]]);
   }

@@ -59,6 +59,11 @@ E2E = {
     # two input files given out of basename order, with different mean lengths: the basename
     # sort, find_k's per-file integer mean (k = 5 here; the pooled mean would give k = 4) and
     # the ids numbered across files (Runner.cpp:253-262, 265-292)
+    # exact copies beside mutants, shuffled: ties of the first maximum of combo 0 and of get_mean
+    # (a copy of the centre scores the maximum wherever it lies; copies share their distance to
+    # the mean), in k-mer and in alignment mode
+    "dup1k": (("dup", 1000, 25, 3, 12, 0.04, 91), ["--id", "0.90"]),
+    "dup_al300": (("dup", 300, 10, 3, 8, 0.03, 92), ["--align", "--id", "0.9"]),
     "two_files": (("multi", [("zz_long", (300, 2000, 10, 0.03, 81)),
                              ("aa_short", (900, 300, 30, 0.03, 82))]), ["--id", "0.90"]),
 }
@@ -133,6 +138,39 @@ def family_reads(n, n_templates, n_families, tmut, mut, seed, length=1000):
         yield b"read%d family_%d template_%d" % (i, t % n_families, t), alpha[mutate(temps[t], mut)].tobytes()
 
 
+def dup_reads(n, n_templates, copies_lo, copies_hi, mut, seed, length=500):
+    """Per template copies_lo..copies_hi exact copies; the other reads are mutants (substitutions,
+    deletions, insertions at rate mut) of the templates in turn; all shuffled."""
+    rng = np.random.default_rng(seed)
+    alpha = np.frombuffer(b"ACGT", dtype=np.uint8)
+    temps = rng.integers(0, 4, size=(n_templates, length), dtype=np.uint8)
+    recs = []
+    for t in range(n_templates):
+        for _ in range(int(rng.integers(copies_lo, copies_hi + 1))):
+            recs.append((t, temps[t]))
+    p = mut / 3.0
+    t = 0
+    while len(recs) < n:
+        s = temps[t % n_templates]
+        r = rng.random(len(s))
+        sub = r < p
+        dele = (r >= p) & (r < 2 * p)
+        ins = (r >= 2 * p) & (r < mut)
+        s2 = s.copy()
+        s2[sub] = rng.integers(0, 4, size=int(sub.sum()), dtype=np.uint8)
+        keep = ~dele
+        reps = np.where(ins, 2, 1)[keep]
+        base = np.repeat(s2[keep], reps)
+        idx = np.cumsum(reps) - 1
+        insm = reps == 2
+        base[idx[insm]] = rng.integers(0, 4, size=int(insm.sum()), dtype=np.uint8)
+        recs.append((t % n_templates, base))
+        t += 1
+    for i, q in enumerate(rng.permutation(len(recs))[:n]):
+        t, s = recs[int(q)]
+        yield b"read%d template_%d" % (i, t), alpha[s].tobytes()
+
+
 def noisy_reads(n, n_templates, mut, seed, length=1000):
     """Reads with what real FASTA carries: lower-case stretches, IUPAC ambiguity letters,
     short N runs (merged into the segment: N -> C) and long N runs (segment splits, 'N' kept),
@@ -180,6 +218,10 @@ def make_input(spec, path):
     if spec[0] == "noisy":
         _, n, t, mut, seed = spec
         synth.write_fasta(path, noisy_reads(n, t, mut, seed))
+        return sha256(path)
+    if spec[0] == "dup":
+        _, n, t, lo, hi, mut, seed = spec
+        synth.write_fasta(path, dup_reads(n, t, lo, hi, mut, seed))
         return sha256(path)
     if spec[0] == "family":
         _, n, t, f, tmut, mut, seed = spec

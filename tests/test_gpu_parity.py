@@ -457,6 +457,8 @@ ACC_CASES = {
     "mixed6k": (("mixed", 6000, 60, 0.06, 72), ["--id", "0.85"]),
     "fam5k": (("family", 5000, 80, 12, 0.10, 0.03, 73), ["--id", "0.90"]),
     "short3k_k3": ((3000, 300, 50, 0.05, 74), ["--id", "0.95", "--kmer", "3"]),
+    # exact copies beside mutants (the e2e golden dup1k): the two paths side by side on ties
+    "dup1k": (("dup", 1000, 25, 3, 12, 0.04, 91), ["--id", "0.90"]),
 }
 
 
