@@ -364,6 +364,45 @@ int mc_nw_align_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, const
 int mc_nw_align_profile(mc_ctx *ctx, double *out /* 3 */, int reset);
 
 /*
+ * THE ALIGNMENTS of mc_nw_align_strands piled up per centre column.  The pairs, the operand rule
+ * (seq1 = the read a[i], its minus-strand string where a_minus[i] != 0; seq2 = the centre b[i] as
+ * written), the batching and its environment caps are mc_nw_align_strands' own; score, len and ids
+ * (m each, may be NULL) are its results bit for bit.
+ * targets: nt distinct point ids, the centres.  A target of L bytes owns L + 1 rows of
+ * MC_PILEUP_CH counters, target t's rows being row_off[t] .. row_off[t + 1]; row_off (nt + 1,
+ * required) receives the prefix sums of L + 1.  Walking a pair's alignment from its first column
+ * with j centre bases consumed so far:
+ *   '=' or 'X'   row j, channel x (the read's byte; x > 3, an N or a raw letter: channel 4); j++
+ *   'D'          row j, channel 5; j++
+ *   an 'I' run of n bases   row j, channel 6 += 1 (reads with an insertion before centre base j;
+ *                row L: after the last base), channel 7 += n (inserted bases); j stays
+ * The alignment is global, so in rows 0 .. L - 1 channels 0 .. 5 add up to the centre's number of
+ * pairs, and row L has channels 0 .. 5 zero.  The counts are integers: the table does not depend
+ * on the order of the pairs or on the batches.
+ * table == NULL: the offsets only, nothing is aligned.  table != NULL with cap_rows < row_off[nt]:
+ * MC_ERR_ARG, row_off valid, table untouched.  Otherwise the table is overwritten (not added to);
+ * a target with no pair gets zero rows, m = 0 a zeroed table.  A duplicate target, an id >= n or a
+ * b[i] that is not a target is MC_ERR_ARG; a pair that alone exceeds the scratch cap
+ * MC_ERR_UNSUPPORTED; both are found before any launch and write nothing, row_off included.  No
+ * sequences: MC_ERR_STATE.
+ * Device: mc_nw_align_strands' forward and traceback kernels; then, instead of copying the
+ * operation words out, a wavefront per pair adds them to a table the context keeps on the device
+ * for the whole call -- two atomics per '=' or 'D' run on per-centre difference arrays, one per
+ * mismatched column, two per 'I' run -- and one kernel per call turns the difference arrays into
+ * counts.  32 bytes per centre base come back, once.  Environment, read per call:
+ * MC_PILEUP_NAIVE=1 issues an atomic per column instead (a measurement aid; the same table).
+ * Timers as mc_nw_align_strands, the pile-up kernels counting as "nw".  mc_nw_pileup_profile:
+ * out[0 .. 2] = device ms of the forward, the traceback and the pile-up kernels since the last reset
+ * (a reset also clears mc_nw_align_profile's two times).
+ */
+#define MC_PILEUP_CH 8
+int mc_nw_pileup_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                         const uint32_t *targets, uint32_t nt, uint64_t *row_off /* nt + 1, required */,
+                         uint32_t *table /* row_off[nt] * MC_PILEUP_CH */, uint64_t cap_rows,
+                         int32_t *score, int32_t *len, int32_t *ids /* m each, may be NULL */);
+int mc_nw_pileup_profile(mc_ctx *ctx, double *out /* 3 */, int reset);
+
+/*
  * Accumulation (ClusterFactory::accumulate, ClusterFactory.cpp:637-714).
  * The bvec of Runner.cpp:342-350 is only ever shrunk after insert_finalize, so the device
  * holds one static candidate order (bin-major, length-sorted within bins) plus an alive

@@ -33,6 +33,7 @@ ASSIGN_MAX_TOP = 8  # MC_ASSIGN_MAX_TOP
 ERR_ARG, ERR_UNSUPPORTED = 1, 6
 ERR_STATE = 3
 CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # MC_CIGAR_*: mc_nw_align_strands' words are run << 4 | op
+PILEUP_CH = 8  # MC_PILEUP_CH: counters per row of mc_nw_pileup_strands' table
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
 
@@ -98,7 +99,7 @@ def gpu_lib():
                      "mc_scan_part", "mc_scan_commit", "mc_comm_unique_id", "mc_comm_create", "mc_comm_allgather",
                      "mc_comm_stats", "mc_comm_destroy", "mc_sync", "mc_assign", "mc_assign_strands",
                      "mc_revcomp_rows", "mc_assign_top", "mc_revcomp_sequences", "mc_nw_identity_strands",
-                     "mc_nw_align_strands", "mc_nw_align_profile"):
+                     "mc_nw_align_strands", "mc_nw_align_profile", "mc_nw_pileup_strands", "mc_nw_pileup_profile"):
             getattr(lib, name).restype = C.c_int
         lib.mc_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
         lib.mc_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -117,6 +118,9 @@ def gpu_lib():
         lib.mc_nw_align_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                             C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mc_nw_align_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.mc_nw_pileup_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mc_nw_pileup_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _bind_steps(lib)
         _gpu = lib
     return _gpu
@@ -190,6 +194,10 @@ def host_lib():
         lib.mcl_assign_paf.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                        C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
                                        C.c_char_p, C.c_char_p, C.c_int]
+        lib.mcl_assign_consensus.restype = C.c_int
+        lib.mcl_assign_consensus.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                             C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
+                                             C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -564,6 +572,39 @@ class Engine:
         self._ck(self.lib.mc_nw_align_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_align_profile")
         return float(out[0]), float(out[1]), float(out[2])
 
+    def nw_pileup_strands(self, a, b, a_minus, targets, table=True):
+        """mc_nw_pileup_strands: nw_align_strands' alignments piled up per centre column ->
+        (table[rows, 8], row_off, score, len, ids).  ``targets``: the distinct centres (every b among
+        them); target t of L bytes owns rows row_off[t] .. row_off[t + 1] (L + 1 of them): channels
+        0..3 the reads' digits over the column, 4 any other read byte, 5 deletions, 6 reads with an
+        insertion before it, 7 the bases they insert.  ``table=False``: the offsets only (table is
+        None, nothing is aligned)."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        am = None if a_minus is None else np.ascontiguousarray(a_minus, np.uint8)
+        tg = np.ascontiguousarray(targets, np.uint32)
+        assert len(b) == len(a) and (am is None or len(am) == len(a))
+        m, nt = len(a), len(tg)
+        off = np.zeros(nt + 1, np.uint64)
+        sc = np.zeros(m, np.int32)
+        ln = np.zeros(m, np.int32)
+        ids = np.zeros(m, np.int32)
+        self._ck(self.lib.mc_nw_pileup_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), _p(tg), C.c_uint32(nt), _p(off), None,
+                                             C.c_uint64(0), None, None, None), "mc_nw_pileup_strands")
+        if not table:
+            return None, off, sc, ln, ids
+        rows = int(off[-1])
+        tab = np.zeros((rows, PILEUP_CH), np.uint32)
+        self._ck(self.lib.mc_nw_pileup_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), _p(tg), C.c_uint32(nt), _p(off),
+                                             _p(tab), C.c_uint64(rows), _p(sc), _p(ln), _p(ids)), "mc_nw_pileup_strands")
+        return tab, off, sc, ln, ids
+
+    def nw_pileup_profile(self, reset=False):
+        """mc_nw_pileup_profile -> (forward ms, traceback ms, pile-up ms) since the last reset."""
+        out = np.zeros(3)
+        self._ck(self.lib.mc_nw_pileup_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_pileup_profile")
+        return float(out[0]), float(out[1]), float(out[2])
+
     def nw_identity_raw(self, a_cat, a_off, b_cat, b_off):
         a_cat = np.ascontiguousarray(a_cat, np.uint8)
         b_cat = np.ascontiguousarray(b_cat, np.uint8)
@@ -589,7 +630,7 @@ class Engine:
 
 
 def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None,
-                 identity=False, min_identity=None, paf=None):
+                 identity=False, min_identity=None, paf=None, consensus=None, pileup=None):
     """Place the reads of the FASTA file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
@@ -607,13 +648,24 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     to the first of its hits that aligns at that identity or more, else it is unassigned.  The stats
     gain ``identity_pairs``, ``identity_cells``, ``rejected`` and the ``identity`` phase.
     ``paf``: meshclust-assign's --paf FILE (mcl_assign_paf; implies ``identity``): one PAF line with a
-    CIGAR (cg:Z:, = X I D) per aligned pair; the stats gain ``paf_pairs`` and ``cigar_ops``."""
+    CIGAR (cg:Z:, = X I D) per aligned pair; the stats gain ``paf_pairs`` and ``cigar_ops``.
+    ``consensus`` / ``pileup``: meshclust-assign's --consensus FILE and --pileup FILE (mcl_assign_consensus;
+    either implies ``identity``): every assigned read is piled up on its centre (mc_nw_pileup_strands);
+    ``consensus`` gets every centre's consensus as FASTA, ``pileup`` the per-column counts of the centres
+    with reads; the stats gain ``consensus_pairs``, ``consensus_centres``, ``consensus_passes``,
+    ``realigned_centres`` and ``insertion_sites``."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    if paf is not None:
+    if consensus is not None or pileup is not None:
+        rc = lib.mcl_assign_consensus(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                      unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
+                                      hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),
+                                      paf.encode() if paf else None, consensus.encode() if consensus else None,
+                                      pileup.encode() if pileup else None, buf, len(buf))
+    elif paf is not None:
         rc = lib.mcl_assign_paf(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                 unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
                                 hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <map>
 #include <mutex>
@@ -299,7 +300,7 @@ int mc_ctx_destroy(mc_ctx *c) {
                  &c->s_c, &c->s_d, &c->s_e, &c->s_f, &c->s_g, &c->s_h, &c->s_i, &c->s_j, &c->s_k, &c->hs, &c->mag_s, &c->sumsq_s, &c->len_s, &c->ticket,
                  &c->msum, &c->ident_s, &c->al_a, &c->al_b, &c->al_out, &c->al_id, &c->ord_ids, &c->acc_out, &c->sp_words, &c->sp_keys,
                  &c->sp_scr, &c->sp_nodes, &c->sp_nn, &c->sp_q, &c->sp_err, &c->u_off, &c->u_mem, &c->nw_items, &c->nw_gran, &c->rc_seq, &c->tr_choice, &c->tr_bnd, &c->tr_ops, &c->tr_pairs, &c->tr_res, &c->tr_idx, &c->tr_dst,
-                 &c->tr_out, &c->tr_err})
+                 &c->tr_out, &c->tr_err, &c->pu_table, &c->pu_diff, &c->pu_rows, &c->pu_toff, &c->pu_roff})
     release(*b);
   if (c->h_scan) (void)hipHostFree(c->h_scan);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -909,18 +910,12 @@ int mc_nw_identity_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, cons
   return MC_OK;
 }
 
-int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
-                        uint32_t *cigar, uint64_t cap, uint64_t *cig_off, int32_t *score, int32_t *len, int32_t *ids) {
-  if (!c || !c->codes.p) return MC_ERR_STATE;
-  if (!cig_off) return MC_ERR_ARG;
-  if (m == 0) {
-    cig_off[0] = 0;
-    return MC_OK;
-  }
-  if (!a || !b) return MC_ERR_ARG;
-  MCG_CHECK(hipSetDevice(c->device));
-  TRY(check_ids(c, a, m));
-  TRY(check_ids(c, b, m));
+// The pairs of mc_nw_align_strands / mc_nw_pileup_strands in batches: the forward pass and the
+// traceback of every batch, then per_batch(i0, mb, res) with the batch's TRACE_RES ints per pair
+// on the host; the batch's pair records, operation words and results are still in c->tr_pairs,
+// c->tr_ops and c->tr_res, its minus-strand strings in c->rc_seq.  `who` names the caller in errors.
+static int align_batches(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                         const std::function<int(uint64_t, uint64_t, const std::vector<int32_t> &)> &per_batch) {
   uint64_t pair_cap = MC_ALIGN_BATCH_PAIRS, scr_cap = MC_ALIGN_SCRATCH_BYTES;
   if (const char *e = getenv("MC_ALIGN_BATCH")) {  // (read per call: the tests put batch ends inside small lists)
     const long long v = atoll(e);
@@ -931,20 +926,11 @@ int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const u
     if (v > 0 && (uint64_t)v < scr_cap) scr_cap = (uint64_t)v;
   }
   auto length = [&](uint32_t id) { return c->h_seq_off[id + 1] - c->h_seq_off[id]; };
-  for (uint64_t i = 0; i < m; i++) {  // before any launch, and before any output is written
-    const uint64_t la = length(a[i]), lb = length(b[i]);
-    if (la + lb >= (1ull << 27) || nw_trace_choice_bytes(la, lb) > scr_cap) {
-      set_error("mc_nw_align_strands: pair " + std::to_string(i) + " (" + std::to_string(la) + " x " + std::to_string(lb) +
-                ") needs " + std::to_string(nw_trace_choice_bytes(la, lb)) + " bytes of choices, the cap is " +
-                std::to_string(scr_cap));
-      return MC_ERR_UNSUPPORTED;
-    }
-  }
   constexpr uint32_t NO_SLOT = 0xffffffffu;
   std::vector<uint32_t> slot;  // point id -> its minus-strand string's slot in this batch's buffer
   if (a_minus) slot.assign(c->n, NO_SLOT);
-  std::vector<uint32_t> uniq, words, nops(m);
-  std::vector<uint64_t> h_off, dst;
+  std::vector<uint32_t> uniq;
+  std::vector<uint64_t> h_off;
   std::vector<TracePair> pairs;
   std::vector<int32_t> res;
   TRY(ensure(c->tr_err, 256));
@@ -1002,9 +988,51 @@ int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const u
     int herr = 0;
     TRY(download_parts(c, {{res.data(), c->tr_res.p, mb * TRACE_RES * 4}, {&herr, c->tr_err.p, 4}}, c->stream));
     if (herr) {
-      set_error("mc_nw_align_strands: a traceback did not reach the matrix's edge within la + lb steps");
+      set_error(std::string(who) + ": a traceback did not reach the matrix's edge within la + lb steps");
       return MC_ERR_HIP;
     }
+    TRY(per_batch(i0, mb, res));
+    i0 = i1;
+  }
+  return MC_OK;
+}
+
+// before any launch, and before any output is written: a pair that alone exceeds the scratch cap
+static int align_check_caps(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t *b, uint64_t m) {
+  uint64_t scr_cap = MC_ALIGN_SCRATCH_BYTES;
+  if (const char *e = getenv("MC_ALIGN_SCRATCH")) {
+    const long long v = atoll(e);
+    if (v > 0 && (uint64_t)v < scr_cap) scr_cap = (uint64_t)v;
+  }
+  auto length = [&](uint32_t id) { return c->h_seq_off[id + 1] - c->h_seq_off[id]; };
+  for (uint64_t i = 0; i < m; i++) {
+    const uint64_t la = length(a[i]), lb = length(b[i]);
+    if (la + lb >= (1ull << 27) || nw_trace_choice_bytes(la, lb) > scr_cap) {
+      set_error(std::string(who) + ": pair " + std::to_string(i) + " (" + std::to_string(la) + " x " + std::to_string(lb) +
+                ") needs " + std::to_string(nw_trace_choice_bytes(la, lb)) + " bytes of choices, the cap is " +
+                std::to_string(scr_cap));
+      return MC_ERR_UNSUPPORTED;
+    }
+  }
+  return MC_OK;
+}
+
+int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                        uint32_t *cigar, uint64_t cap, uint64_t *cig_off, int32_t *score, int32_t *len, int32_t *ids) {
+  if (!c || !c->codes.p) return MC_ERR_STATE;
+  if (!cig_off) return MC_ERR_ARG;
+  if (m == 0) {
+    cig_off[0] = 0;
+    return MC_OK;
+  }
+  if (!a || !b) return MC_ERR_ARG;
+  MCG_CHECK(hipSetDevice(c->device));
+  TRY(check_ids(c, a, m));
+  TRY(check_ids(c, b, m));
+  TRY(align_check_caps(c, "mc_nw_align_strands", a, b, m));
+  std::vector<uint32_t> words, nops(m);
+  std::vector<uint64_t> dst;
+  TRY(align_batches(c, "mc_nw_align_strands", a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
     dst.resize(mb);
     uint64_t tot = 0;
     for (uint64_t k = 0; k < mb; k++) {
@@ -1025,8 +1053,8 @@ int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const u
       MCG_CHECK(hipMemcpyAsync(words.data() + at, c->tr_out.p, tot * 4, hipMemcpyDeviceToHost, c->stream));
       MCG_CHECK(hipStreamSynchronize(c->stream));
     }
-    i0 = i1;
-  }
+    return (int)MC_OK;
+  }));
   flush_timers(c);
   cig_off[0] = 0;
   for (uint64_t i = 0; i < m; i++) cig_off[i + 1] = cig_off[i] + nops[i];
@@ -1041,6 +1069,81 @@ int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const u
   return MC_OK;
 }
 
+int mc_nw_pileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                         const uint32_t *targets, uint32_t nt, uint64_t *row_off, uint32_t *table, uint64_t cap_rows,
+                         int32_t *score, int32_t *len, int32_t *ids) {
+  if (!c || !c->codes.p) return MC_ERR_STATE;
+  if (!row_off || (nt && !targets) || (m && (!a || !b))) return MC_ERR_ARG;
+  MCG_CHECK(hipSetDevice(c->device));
+  TRY(check_ids(c, targets, nt));
+  TRY(check_ids(c, a, m));
+  TRY(check_ids(c, b, m));
+  constexpr uint32_t NO_TARGET = 0xffffffffu;
+  std::vector<uint32_t> tindex(c->n, NO_TARGET);  // point id -> its place among the targets
+  for (uint32_t t = 0; t < nt; t++) {
+    if (tindex[targets[t]] != NO_TARGET) {
+      set_error("mc_nw_pileup_strands: point " + std::to_string(targets[t]) + " is listed twice among the targets");
+      return MC_ERR_ARG;
+    }
+    tindex[targets[t]] = t;
+  }
+  for (uint64_t i = 0; i < m; i++)
+    if (tindex[b[i]] == NO_TARGET) {
+      set_error("mc_nw_pileup_strands: pair " + std::to_string(i) + "'s seq2, point " + std::to_string(b[i]) +
+                ", is not among the targets");
+      return MC_ERR_ARG;
+    }
+  TRY(align_check_caps(c, "mc_nw_pileup_strands", a, b, m));
+  std::vector<uint64_t> toff(nt);
+  row_off[0] = 0;
+  for (uint32_t t = 0; t < nt; t++) {
+    toff[t] = c->h_seq_off[targets[t]];
+    row_off[t + 1] = row_off[t] + (c->h_seq_off[targets[t] + 1] - c->h_seq_off[targets[t]]) + 1;
+  }
+  if (!table) return MC_OK;
+  const uint64_t rows = row_off[nt];
+  if (cap_rows < rows) {
+    set_error("mc_nw_pileup_strands: table holds " + std::to_string(cap_rows) + " rows, the targets have " + std::to_string(rows));
+    return MC_ERR_ARG;
+  }
+  if (rows == 0) return MC_OK;
+  if (m == 0) {
+    memset(table, 0, rows * MC_PILEUP_CH * 4);
+    return MC_OK;
+  }
+  // the table and the two difference arrays stay on the device for the whole call: zeroed once,
+  // every batch adds to them, one download at the end
+  TRY(ensure(c->pu_table, rows * MC_PILEUP_CH * 4 + 64));
+  TRY(ensure(c->pu_diff, rows * 8 + 64));
+  uint32_t *d_table = (uint32_t *)c->pu_table.p;
+  int32_t *d_deq = (int32_t *)c->pu_diff.p, *d_ddel = d_deq + rows;
+  MCG_CHECK(hipMemsetAsync(d_table, 0, rows * MC_PILEUP_CH * 4, c->stream));
+  MCG_CHECK(hipMemsetAsync(d_deq, 0, rows * 8, c->stream));
+  const char *nv = getenv("MC_PILEUP_NAIVE");  // (a measurement aid: an atomic per column; the same table)
+  const bool naive = nv && atoi(nv) != 0;
+  std::vector<uint64_t> rowbase;
+  TRY(align_batches(c, "mc_nw_pileup_strands", a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
+    rowbase.resize(mb);
+    for (uint64_t k = 0; k < mb; k++) {
+      rowbase[k] = row_off[tindex[b[i0 + k]]];
+      if (score) score[i0 + k] = res[k * TRACE_RES];
+      if (len) len[i0 + k] = res[k * TRACE_RES + 1];
+      if (ids) ids[i0 + k] = res[k * TRACE_RES + 2];
+    }
+    TRY(upload(c, c->pu_rows, rowbase.data(), mb, c->stream));
+    return launch_nw_pileup(c, (uint32_t)mb, (const TracePair *)c->tr_pairs.p, (const uint8_t *)c->rc_seq.p,
+                            (const uint32_t *)c->tr_ops.p, (const int32_t *)c->tr_res.p, (const uint64_t *)c->pu_rows.p, d_table,
+                            d_deq, d_ddel, naive);
+  }));
+  TRY(upload(c, c->pu_toff, toff.data(), nt, c->stream));
+  TRY(upload(c, c->pu_roff, row_off, (size_t)nt + 1, c->stream));
+  TRY(launch_nw_pileup_finish(c, nt, (const uint64_t *)c->pu_toff.p, (const uint64_t *)c->pu_roff.p, d_table, d_deq, d_ddel));
+  MCG_CHECK(hipMemcpyAsync(table, d_table, rows * MC_PILEUP_CH * 4, hipMemcpyDeviceToHost, c->stream));
+  MCG_CHECK(hipStreamSynchronize(c->stream));
+  flush_timers(c);
+  return MC_OK;
+}
+
 int mc_nw_align_profile(mc_ctx *c, double *out, int reset) {
   if (!c || !out) return MC_ERR_ARG;
   (void)hipStreamSynchronize(c->stream);
@@ -1052,6 +1155,18 @@ int mc_nw_align_profile(mc_ctx *c, double *out, int reset) {
     c->fam_ms[F_NW_FWD] = c->fam_ms[F_NW_TB] = c->fam_n[F_NW_FWD] = c->fam_n[F_NW_TB] = 0;
     c->tr_choice_bytes = 0;
   }
+  return MC_OK;
+}
+
+int mc_nw_pileup_profile(mc_ctx *c, double *out, int reset) {
+  if (!c || !out) return MC_ERR_ARG;
+  (void)hipStreamSynchronize(c->stream);
+  flush_timers(c);
+  out[0] = c->fam_ms[F_NW_FWD];
+  out[1] = c->fam_ms[F_NW_TB];
+  out[2] = c->fam_ms[F_NW_PU];
+  if (reset)
+    for (int f : {F_NW_FWD, F_NW_TB, F_NW_PU}) c->fam_ms[f] = c->fam_n[f] = 0;
   return MC_OK;
 }
 

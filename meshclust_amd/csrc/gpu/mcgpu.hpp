@@ -29,8 +29,9 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // Kernel families for the device timers (mc_timers): ms and launch count per family.
 // F_LAYOUT: the static bvec-order copies of the rows (build_static), after K1
 // F_NW_FWD / F_NW_TB: the forward and traceback kernels of nwtrace.hip; they count as F_NW in
-// mc_timers and are kept apart only for mc_nw_align_profile
-enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NALL };
+// mc_timers and are kept apart only for mc_nw_align_profile; F_NW_PU: the pile-up kernels of
+// pileup.hip, likewise part of F_NW and kept apart for mc_nw_pileup_profile
+enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NALL };
 
 // Classifier in the form the kernels consume (mc_classifier + the exact decision threshold).
 struct DevClassifier {
@@ -176,6 +177,10 @@ struct mc_ctx {
   // results, launch lists, output offsets and packed operations; the error word
   mcg::Buf tr_choice, tr_bnd, tr_ops, tr_pairs, tr_res, tr_idx, tr_dst, tr_out, tr_err;
   double tr_choice_bytes = 0;  // choice bytes written since the last mc_nw_align_profile reset
+  // mc_nw_pileup_strands: the call's table (8 counters per row) and its two difference arrays
+  // ('=' and 'D' coverage, an int per row), a batch's row base per pair, the targets' code offsets
+  // and row offsets
+  mcg::Buf pu_table, pu_diff, pu_rows, pu_toff, pu_roff;
   // mc_update_iteration's member lists on the device and their host shadow: re-uploaded only
   // when a merge changed them (cleared when sequences are loaded: the ids were checked against n)
   mcg::Buf u_off, u_mem;
@@ -273,6 +278,15 @@ int launch_nw_trace(mc_ctx *c, const std::vector<TracePair> &h_pairs, const Trac
                     uint8_t *d_choice, int *d_bnd, uint32_t *d_ops, int32_t *d_res, int *d_err);
 int launch_nw_pack(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint32_t *d_ops, const int32_t *d_res,
                    const uint64_t *d_dst, uint32_t *d_out);
+
+// pileup.hip: the pairs of a batch (after launch_nw_trace) added to the call's table and
+// difference arrays, pair p's rows starting at d_rowbase[p]; naive: every column its own atomic.
+// launch_nw_pileup_finish turns the difference arrays of every target into the '=' and 'D' counts.
+int launch_nw_pileup(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint8_t *d_rc, const uint32_t *d_ops,
+                     const int32_t *d_res, const uint64_t *d_rowbase, uint32_t *d_table, int32_t *d_deq, int32_t *d_ddel,
+                     bool naive);
+int launch_nw_pileup_finish(mc_ctx *c, uint32_t nt, const uint64_t *d_tgt_off, const uint64_t *d_row_off, uint32_t *d_table,
+                            const int32_t *d_deq, const int32_t *d_ddel);
 
 }  // namespace mcg
 

@@ -14,8 +14,10 @@
 #endif
 
 #include "cigar.hpp"
+#include "consensus.hpp"
 #include "fasta.hpp"
 #include "model.hpp"
+#include "revseq.hpp"
 #include "topk.hpp"
 #include "verify.hpp"
 
@@ -23,8 +25,8 @@ namespace mc {
 
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
-    "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--device N] "
-    "[--threads N] [--stats-json FILE] [--quiet]\n"
+    "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--consensus FILE] "
+    "[--pileup FILE] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
     "  --top K --hits FILE  (given together, K = 1..8) also write the K best similar centres of every read to\n"
     "                  FILE: read, rank, centre, cluster index, combo 0 (and the strand with --both-strands)\n"
@@ -33,7 +35,12 @@ static const char *kUsage =
     "  --min-identity X  (0 <= X <= 1, implies --identity) assign a read to the first of its hits (the --top K\n"
     "                  best, or the best one) that aligns at identity X or more; none: the read is unassigned\n"
     "  --paf FILE      (implies --identity) also write every aligned (read, centre) pair as a PAF line with its\n"
-    "                  CIGAR (cg:Z:, = X I D); on - the CIGAR runs along the reverse-complemented read\n";
+    "                  CIGAR (cg:Z:, = X I D); on - the CIGAR runs along the reverse-complemented read\n"
+    "  --consensus FILE  (implies --identity) pile the assigned reads up on their centres and write every centre's\n"
+    "                  consensus as FASTA: >NAME depth=D sub=S del=X ins=I (a centre without reads: its own sequence)\n"
+    "  --pileup FILE   (implies the --consensus pass) the counts behind it, for centres with reads: centre, column\n"
+    "                  (the row after the last base: L+1, base *), centre base, depth, A, C, G, T, N, del, ins_reads,\n"
+    "                  ins_bases\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
   AssignOptions o;
@@ -66,6 +73,12 @@ AssignOptions parse_assign_options(int argc, char **argv) {
       o.identity = true;
     } else if (arg == "--paf" && has) {
       o.paf = argv[++i];
+      o.identity = true;
+    } else if (arg == "--consensus" && has) {
+      o.consensus = argv[++i];
+      o.identity = true;
+    } else if (arg == "--pileup" && has) {
+      o.pileup = argv[++i];
       o.identity = true;
     } else {
       struct stat st;
@@ -134,6 +147,118 @@ static void assign_by_pairs(mc_ctx *ctx, const Dataset &ds, uint32_t C, uint64_t
     if (a.size() >= batch) flush();
   }
   flush();
+}
+
+static void write_text(const std::string &path, const std::string &text) {
+  FILE *f = fopen(path.c_str(), "w");
+  if (!f) throw Error("cannot write " + path + ": " + strerror(errno), 1);
+  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+  if (fclose(f) != 0 || !ok) throw Error("cannot write " + path, 1);
+}
+
+// the expanded bytes of one record (fasta.hpp unpack_codes, for one id)
+static std::vector<uint8_t> expanded_bytes(const Dataset &ds, uint32_t id) {
+  const uint64_t len = ds.seq_off[id + 1] - ds.seq_off[id];
+  std::vector<uint8_t> out(len);
+  const uint32_t *w = ds.packed.data() + ds.pk_off[id];
+  for (uint64_t j = 0; j < len; j++) out[j] = (uint8_t)((w[j / 16] >> (2 * (j % 16))) & 3u);
+  auto e = std::lower_bound(ds.exc_pos.begin(), ds.exc_pos.end(), ds.seq_off[id]);
+  for (; e != ds.exc_pos.end() && *e < ds.seq_off[id + 1]; ++e) out[*e - ds.seq_off[id]] = ds.exc_val[e - ds.exc_pos.begin()];
+  return out;
+}
+
+// --consensus / --pileup: the pairs (read pa, centre pb < C, strand pm) piled up on the centres
+// 0 .. C-1 in one mc_nw_pileup_strands call; pid (if given) receives every pair's ids / len.
+// Centres with an insertion site have their pairs aligned again for the inserted bases.
+static void pileup_outputs(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::vector<uint32_t> &pa,
+                           const std::vector<uint32_t> &pb, const std::vector<uint8_t> &pm, const AssignOptions &opt,
+                           AssignResult &r, std::vector<double> *pid) {
+  const size_t m = pa.size();
+  std::vector<uint32_t> targets(C);
+  std::vector<uint64_t> row_off((size_t)C + 1, 0);
+  uint64_t rows = 0;
+  for (uint32_t j = 0; j < C; j++) {
+    targets[j] = j;
+    rows += ds.lengths[j] + 1;
+  }
+  std::vector<uint32_t> table(rows * MC_PILEUP_CH);
+  std::vector<int32_t> ln(m), idn(m);
+  check(mc_nw_pileup_strands(ctx, pa.data(), pb.data(), pm.data(), m, targets.data(), C, row_off.data(), table.data(), rows,
+                             nullptr, ln.data(), idn.data()),
+        "mc_nw_pileup_strands");
+  if (pid)
+    for (size_t p = 0; p < m; p++) (*pid)[p] = (double)idn[p] / (double)ln[p];
+  r.consensus = true;
+  r.consensus_pairs = m;
+  // a centre's pairs: from[c] .. from[c + 1] of `of` (a counting sort, input order kept)
+  std::vector<uint64_t> from((size_t)C + 1, 0);
+  for (size_t p = 0; p < m; p++) from[pb[p] + 1]++;
+  for (uint32_t j = 0; j < C; j++) from[j + 1] += from[j];
+  std::vector<size_t> of(m);
+  {
+    std::vector<uint64_t> at(from.begin(), from.end() - 1);
+    for (size_t p = 0; p < m; p++) of[at[pb[p]]++] = p;
+  }
+  std::string fa, tsv;
+  char num[160];
+  std::vector<uint32_t> qa, qb, cig;
+  std::vector<uint8_t> qm, rcb;
+  std::vector<uint64_t> off;
+  for (uint32_t j = 0; j < C; j++) {
+    const uint64_t L = ds.lengths[j], depth = from[j + 1] - from[j];
+    const uint32_t *rw = table.data() + row_off[j] * MC_PILEUP_CH;
+    const std::vector<uint8_t> cen = expanded_bytes(ds, j);
+    InsertionRuns runs;
+    if (depth > 0) {
+      r.consensus_centres++;
+      const std::vector<uint64_t> sites = insertion_sites(rw, L, depth);
+      if (!sites.empty()) {  // the inserted bases are not in the table: this centre's alignments once more
+        r.realigned_centres++;
+        qa.clear(), qb.clear(), qm.clear();
+        uint64_t cap = 0;
+        for (uint64_t k = from[j]; k < from[j + 1]; k++) {
+          qa.push_back(pa[of[k]]);
+          qb.push_back(j);
+          qm.push_back(pm[of[k]]);
+          cap += ds.lengths[pa[of[k]]] + L;
+        }
+        cig.resize(cap);
+        off.assign(depth + 1, 0);
+        check(mc_nw_align_strands(ctx, qa.data(), qb.data(), qm.data(), depth, cig.data(), cap, off.data(), nullptr, nullptr,
+                                  nullptr),
+              "mc_nw_align_strands");
+        for (uint64_t k = 0; k < depth; k++) {
+          std::vector<uint8_t> rd = expanded_bytes(ds, qa[k]);
+          if (qm[k]) {
+            rcb.resize(rd.size());
+            revseq(rd.data(), rd.size(), rcb.data());
+            rd.swap(rcb);
+          }
+          insertion_runs(cig.data() + off[k], off[k + 1] - off[k], rd.data(), sites, runs);
+        }
+      }
+    }
+    const Consensus cs = consensus_of(cen.data(), L, rw, depth, runs);
+    r.insertion_sites += cs.ins;
+    if (!opt.consensus.empty()) {
+      fa.append(ds.headers[j]);
+      snprintf(num, sizeof num, " depth=%llu sub=%llu del=%llu ins=%llu\n", (unsigned long long)depth, (unsigned long long)cs.sub,
+               (unsigned long long)cs.del, (unsigned long long)cs.ins);
+      fa += num;
+      fa += cs.seq;
+      fa += '\n';
+    }
+    if (!opt.pileup.empty() && depth > 0)
+      for (uint64_t t = 0; t <= L; t++) {
+        const uint32_t *x = rw + t * MC_PILEUP_CH;
+        tsv.append(ds.headers[j].substr(1));
+        snprintf(num, sizeof num, "\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", (unsigned long long)(t + 1),
+                 t < L ? pileup_base_char(cen[t]) : '*', (unsigned long long)depth, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7]);
+        tsv += num;
+      }
+  }
+  if (!opt.consensus.empty()) write_text(opt.consensus, fa);
+  if (!opt.pileup.empty()) write_text(opt.pileup, tsv);
 }
 
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
@@ -249,7 +374,9 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   const uint32_t Kc = K > 0 ? K : 1;
   std::vector<double> cand_id;  // Kc slots per read, as hit / hit_val
   std::vector<double> ident_q(M, -1.0);
-  if (opt.identity) {
+  const bool pile = !opt.consensus.empty() || !opt.pileup.empty();
+  const bool pile_only = pile && K == 0 && opt.min_identity < 0 && opt.paf.empty();
+  if (opt.identity || pile) {
     r.identity = true;
     const uint32_t *cj = K > 0 ? hit.data() : best.data();
     const double *cv = K > 0 ? hit_val.data() : val.data();
@@ -268,7 +395,12 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
     }
     r.identity_pairs = pa.size();
     std::vector<double> pid(pa.size(), 0.0);
-    if (opt.paf.empty()) {
+    if (pile_only) {
+      // the reported pairs are the assigned reads' own: the pile-up is the one alignment pass, and
+      // the identity its ids / len, the division mc_nw_identity does
+      r.consensus_passes = 1;
+      pileup_outputs(ctx, ds, (uint32_t)C, pa, pb, pm, opt, r, &pid);
+    } else if (opt.paf.empty()) {
       check(mc_nw_identity_strands(ctx, pa.data(), pb.data(), pm.data(), pa.size(), pid.data(), nullptr, nullptr),
             "mc_nw_identity_strands");
     } else {
@@ -351,6 +483,17 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
       }
       if (pick >= 0) ident_q[q] = cand_id[q * Kc + pick];
     }
+    if (pile && !pile_only) {  // a second pass, over the pairs the selection kept
+      r.consensus_passes = 2;
+      pa.clear(), pb.clear(), pm.clear();
+      for (uint64_t q = 0; q < M; q++)
+        if (best[q] != MC_ASSIGN_NONE) {
+          pa.push_back((uint32_t)(C + q));
+          pb.push_back(best[q]);
+          pm.push_back(opt.both_strands ? strand[q] : 0);
+        }
+      pileup_outputs(ctx, ds, (uint32_t)C, pa, pb, pm, opt, r, nullptr);
+    }
   }
   r.identity_ms = ms_since(t0);
   t0 = std::chrono::steady_clock::now();
@@ -420,7 +563,7 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
 
 std::string assign_stats_json(const AssignResult &r) {
   // (one strand, no --top, no --identity: exactly the keys there were before any of the options)
-  char b[1280], s[448] = "", idms[48] = "";
+  char b[1536], s[704] = "", idms[48] = "";
   int n = 0;
   if (r.strands != MC_STRAND_PLUS)
     n = snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
@@ -429,8 +572,14 @@ std::string assign_stats_json(const AssignResult &r) {
     n += snprintf(s + n, sizeof s - n, "\"identity_pairs\": %llu, \"identity_cells\": %llu, \"rejected\": %llu, ",
                   (unsigned long long)r.identity_pairs, (unsigned long long)r.identity_cells, (unsigned long long)r.rejected);
     if (r.paf)
-      snprintf(s + n, sizeof s - n, "\"paf_pairs\": %llu, \"cigar_ops\": %llu, ", (unsigned long long)r.paf_pairs,
-               (unsigned long long)r.cigar_ops);
+      n += snprintf(s + n, sizeof s - n, "\"paf_pairs\": %llu, \"cigar_ops\": %llu, ", (unsigned long long)r.paf_pairs,
+                    (unsigned long long)r.cigar_ops);
+    if (r.consensus)
+      snprintf(s + n, sizeof s - n,
+               "\"consensus_pairs\": %llu, \"consensus_centres\": %llu, \"consensus_passes\": %d, \"realigned_centres\": %llu, "
+               "\"insertion_sites\": %llu, ",
+               (unsigned long long)r.consensus_pairs, (unsigned long long)r.consensus_centres, r.consensus_passes,
+               (unsigned long long)r.realigned_centres, (unsigned long long)r.insertion_sites);
     snprintf(idms, sizeof idms, "\"identity\": %.3f, ", r.identity_ms);
   }
   snprintf(b, sizeof b,

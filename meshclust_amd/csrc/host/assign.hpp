@@ -20,6 +20,8 @@ struct AssignOptions {
   bool identity = false;      // --identity: align every reported (read, centre, strand), report the identity
   double min_identity = -1;   // --min-identity X (0..1, implies identity; negative: off): verify.hpp
   std::string paf;            // --paf FILE (implies identity): the alignments of the reported pairs as PAF
+  std::string consensus;      // --consensus FILE (implies identity): a consensus per centre from its assigned reads, FASTA
+  std::string pileup;         // --pileup FILE (implies the consensus pass): the per-column counts behind it, TSV
 };
 
 struct AssignResult {
@@ -36,6 +38,10 @@ struct AssignResult {
   uint64_t identity_pairs = 0, identity_cells = 0, rejected = 0;  // reads with a hit but none at >= X
   bool paf = false;              // --paf: lines written, operation words of their CIGARs
   uint64_t paf_pairs = 0, cigar_ops = 0;
+  bool consensus = false;        // --consensus / --pileup: pairs piled up, centres with a read, alignment passes
+  uint64_t consensus_pairs = 0, consensus_centres = 0;  // (1: the pile-up gave the identities too; 2: it came second),
+  int consensus_passes = 0;                             // centres re-aligned for their inserted bases, sites applied
+  uint64_t realigned_centres = 0, insertion_sites = 0;
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
   double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0;
 };
@@ -60,6 +66,16 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // ascending: read, its length, 0, its length, strand, centre, its length, 0, its length, ids, len,
 // 255, AS:i:score, rk:i:rank, cg:Z:CIGAR (cigar.hpp).  On '-' the CIGAR runs along the
 // reverse-complemented read.  min_identity selects as without paf; the PAF lists every aligned pair.
+// With consensus / pileup (mc_nw_pileup_strands; either implies identity) the pair (read, its final
+// centre, its strand) of every assigned read -- after min_identity's selection -- is piled up per
+// centre column.  consensus gets every centre in centres-file order as FASTA, ">NAME depth=D sub=S
+// del=X ins=I" and the consensus of consensus.hpp (a centre without reads: its own sequence); pileup
+// gets, for centres with a read, one line per row: centre, column from 1 (L + 1 with base *), centre
+// base, depth, A, C, G, T, N, del, ins_reads, ins_bases.  With no top, min_identity or paf the
+// pile-up is the only alignment pass and the identity column is its ids / len (the same doubles);
+// otherwise it is a second pass over the selected pairs ("consensus_passes" 1 or 2 in the stats).
+// Centres with an insertion site are re-aligned with mc_nw_align_strands for the inserted bases
+// ("realigned_centres").
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
 std::string assign_stats_json(const AssignResult &r);
 int assign_main(int argc, char **argv);

@@ -16,10 +16,13 @@ extern "C" {
 // error code with {"error": ...} in stats; an error never ends the calling process.
 static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
                         int threads, const char *tsv, const char *unassigned, bool both_strands, int top, const char *hits,
-                        int identity, double min_identity, const char *paf, char *stats, int cap) {
+                        int identity, double min_identity, const char *paf, const char *consensus, const char *pileup,
+                        char *stats, int cap) {
   try {
     mc::AssignOptions opt;
     if (paf) opt.paf = paf;
+    if (consensus) opt.consensus = consensus;
+    if (pileup) opt.pileup = pileup;
     opt.both_strands = both_strands;
     opt.top = top;
     if (hits) opt.hits = hits;
@@ -27,7 +30,7 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
       throw mc::Error("mcl_assign_top: top (1 .. MC_ASSIGN_MAX_TOP) and hits are given together", 1);
     if (!(min_identity <= 1)) throw mc::Error("mcl_assign_identity: min_identity is 0 .. 1 (negative: off)", 1);
     opt.min_identity = min_identity < 0 ? -1 : min_identity;
-    opt.identity = identity != 0 || min_identity >= 0 || !opt.paf.empty();
+    opt.identity = identity != 0 || min_identity >= 0 || !opt.paf.empty() || !opt.consensus.empty() || !opt.pileup.empty();
     opt.model = model ? model : "";
     opt.centres = centres ? centres : "";
     for (int i = 0; i < nreads; i++) opt.reads.push_back(reads[i]);
@@ -53,7 +56,7 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
 
 int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
                const char *tsv, const char *unassigned, char *stats, int cap) {
-  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, false, 0, nullptr, 0, -1.0, nullptr, stats, cap);
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, false, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, stats, cap);
 }
 
 // mcl_assign with meshclust-assign's --both-strands when both_strands is non-zero (mc_assign_strands
@@ -61,7 +64,7 @@ int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *
 // Where only the pair list applies it returns 2 with the reason in stats.
 int mcl_assign_strands(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
                        int threads, const char *tsv, const char *unassigned, int both_strands, char *stats, int cap) {
-  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, 0, nullptr, 0, -1.0, nullptr, stats, cap);
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, stats, cap);
 }
 
 // mcl_assign_strands with meshclust-assign's --top `top` --hits `hits` (mc_assign_top): the TSV is
@@ -70,8 +73,8 @@ int mcl_assign_strands(mc_ctx *ctx, const char *model, const char *centres, cons
 int mcl_assign_top(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
                    const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, char *stats,
                    int cap) {
-  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, 0, -1.0, nullptr, stats,
-                      cap);
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, 0, -1.0, nullptr, nullptr,
+                      nullptr, stats, cap);
 }
 
 // mcl_assign_top with meshclust-assign's --identity (identity non-zero) and --min-identity
@@ -82,7 +85,7 @@ int mcl_assign_identity(mc_ctx *ctx, const char *model, const char *centres, con
                         const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
                         double min_identity, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, nullptr, stats, cap);
+                      min_identity, nullptr, nullptr, nullptr, stats, cap);
 }
 
 // mcl_assign_identity with meshclust-assign's --paf `paf` (mc_nw_align_strands; implies identity):
@@ -92,7 +95,19 @@ int mcl_assign_paf(mc_ctx *ctx, const char *model, const char *centres, const ch
                    const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
                    double min_identity, const char *paf, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, paf, stats, cap);
+                      min_identity, paf, nullptr, nullptr, stats, cap);
+}
+
+// mcl_assign_paf with meshclust-assign's --consensus `consensus` and --pileup `pileup`
+// (mc_nw_pileup_strands; either implies identity, either may be NULL): the consensus FASTA of every
+// centre and the per-column counts of the centres with reads; the summary gains "consensus_pairs",
+// "consensus_centres", "consensus_passes", "realigned_centres" and "insertion_sites".  Both NULL is
+// mcl_assign_paf.
+int mcl_assign_consensus(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
+                         const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
+                         double min_identity, const char *paf, const char *consensus, const char *pileup, char *stats, int cap) {
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
+                      min_identity, paf, consensus, pileup, stats, cap);
 }
 
 // Records ids[0..n) of a parsed dataset (mcl_parse) as FASTA: header lines unchanged, each

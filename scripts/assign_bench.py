@@ -43,6 +43,14 @@ the path).  Adds the forward and the traceback kernels' device times (mc_nw_alig
 choice bytes the forward pass writes per second, DP cells per second and the ratios; len / ids are
 checked against mc_nw_identity_strands first.
 
+--pileup also times mc_nw_pileup_strands (the pile-up behind meshclust-assign --consensus) over the
+same (read, its centre) pairs, one pair per read, every second read on the minus strand, beside
+mc_nw_align_strands with its operation words on those pairs.  score / len / ids of the two calls
+are compared first, and the table's column sums with the sums of the words.  Adds the forward,
+traceback and pile-up (+ finish) device times (mc_nw_pileup_profile), the same with an atomic per
+column (MC_PILEUP_NAIVE=1; the tables are compared), the bytes each call returns to the host and
+the atomics issued per pair against la + lb.
+
 Under rocprofv3 set MC_ACCUM_PLAIN_LAUNCH=1, as scripts/prof_round.sh does: the clustering's
 cooperative launch otherwise faults the profiler's exit handler, after the
 profile is written.
@@ -210,6 +218,68 @@ def align_phase(eng, lens, centres, queries, best, a):
     return out
 
 
+def pileup_phase(eng, lens, centres, queries, best, a):
+    """Times mc_nw_pileup_strands over every assigned read and its centre (every second read on the
+    minus strand) beside mc_nw_align_strands with its words on the same pairs -> the keys for the line."""
+    has = best != M.ASSIGN_NONE
+    qa, cb = queries[has], centres[best[has]]
+    am = (np.arange(len(qa)) % 2).astype(np.uint8)
+    targets = np.unique(cb)
+    out = {"pileup_pairs": int(len(qa)), "pileup_targets": int(len(targets))}
+    res = {}
+    for name in ("align", "pileup", "pileup_naive"):
+        if name == "pileup_naive":
+            os.environ["MC_PILEUP_NAIVE"] = "1"
+        wall, fwd, tb, pu = [], [], [], []
+        for r in range(a.warmup + a.rounds):
+            eng.nw_pileup_profile(reset=True)
+            t0 = time.perf_counter()
+            got = eng.nw_align_strands(qa, cb, am) if name == "align" else eng.nw_pileup_strands(qa, cb, am, targets)
+            w = time.perf_counter() - t0
+            pr = eng.nw_pileup_profile()
+            if r >= a.warmup:
+                wall.append(w)
+                fwd.append(pr[0])
+                tb.append(pr[1])
+                pu.append(pr[2])
+        os.environ.pop("MC_PILEUP_NAIVE", None)
+        res[name] = got
+        out[name + "_call_wall_ms"] = round(1e3 * float(np.median(wall)), 3)
+        out[name + "_call_wall_ms_all"] = [round(1e3 * x, 3) for x in wall]
+        out[name + "_forward_device_ms"] = round(float(np.median(fwd)), 3)
+        out[name + "_traceback_device_ms" + ("_with_pack" if name == "align" else "")] = round(float(np.median(tb)), 3)
+        out[name + "_traceback_device_ms_all"] = [round(x, 3) for x in tb]
+        if name != "align":
+            out[name + "_pileup_finish_device_ms"] = round(float(np.median(pu)), 3)
+            out[name + "_pileup_finish_device_ms_all"] = [round(x, 3) for x in pu]
+    words, off, sc, ln, ids = res["align"]
+    tab, row_off, p_sc, p_ln, p_ids = res["pileup"]
+    assert np.array_equal(sc, p_sc) and np.array_equal(ln, p_ln) and np.array_equal(ids, p_ids), "integers differ from mc_nw_align_strands"
+    assert all(np.array_equal(x, y) for x, y in zip(res["pileup"], res["pileup_naive"])), "the per-column form gives another table"
+    run, op = (words >> 4).astype(np.int64), words & 15
+    sums = {k: int(run[op == v].sum()) for k, v in (("eq", M.CIGAR_EQ), ("x", M.CIGAR_X), ("i", M.CIGAR_I), ("d", M.CIGAR_D))}
+    n_i = int((op == M.CIGAR_I).sum())
+    assert int(tab[:, :5].sum()) == sums["eq"] + sums["x"] and int(tab[:, 5].sum()) == sums["d"], "column sums differ from the words"
+    assert int(tab[:, 6].sum()) == n_i and int(tab[:, 7].sum()) == sums["i"], "insertion sums differ from the words"
+    assert int(tab[:, :6].sum()) == int(lens[cb].sum()), "a centre column is not covered once per pair"
+    m = len(qa)
+    atomics = 2 * int((op != M.CIGAR_X).sum()) + sums["x"]
+    bases = int(lens[qa].sum()) + int(lens[cb].sum())
+    out["pileup_outputs_equal"] = True
+    out["align_bytes_to_host"] = int(words.nbytes + off.nbytes + 12 * m)
+    out["pileup_bytes_to_host"] = int(tab.nbytes + row_off.nbytes + 12 * m)
+    out["pileup_table_rows"] = int(row_off[-1])
+    out["pileup_atomics_per_pair"] = round(atomics / m, 2)
+    out["pileup_naive_atomics_per_pair"] = round((sums["eq"] + sums["x"] + sums["d"] + 2 * n_i) / m, 2)
+    out["pileup_bases_per_pair"] = round(bases / m, 2)
+    out["pileup_runs_per_pair"] = round(len(words) / m, 2)
+    out["pileup_finish_over_pack_and_download_ms"] = [
+        out["pileup_pileup_finish_device_ms"],
+        round(out["align_call_wall_ms"] - out["align_forward_device_ms"] - out["pileup_traceback_device_ms"], 3)]
+    out["pileup_call_over_align_call"] = round(out["pileup_call_wall_ms"] / out["align_call_wall_ms"], 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=sorted(bench.WORKLOADS), default="B")
@@ -232,6 +302,10 @@ def main():
                     help="also time mc_nw_align_strands (the alignments behind --paf) over every read and its centre, every "
                          "second read on the minus strand, against mc_nw_identity_strands on the same pairs: forward and "
                          "traceback device time, choice bytes per second, and the ratios")
+    ap.add_argument("--pileup", action="store_true",
+                    help="also time mc_nw_pileup_strands (the pile-up behind --consensus) over every read and its centre beside "
+                         "mc_nw_align_strands on the same pairs: forward, traceback and pile-up device time, bytes returned, "
+                         "atomics per pair, and the same with an atomic per column")
     a = ap.parse_args()
     n, templates, seed = bench.WORKLOADS[a.workload]
     fasta = bench.ensure_fasta(n, 1000, templates, 0.03, seed)
@@ -392,6 +466,8 @@ def main():
         line.update(identity_phase(eng, ds, ptr, seq_off, lens, centres, queries, best, a, d_us))
     if a.align:
         line.update(align_phase(eng, lens, centres, queries, best, a))
+    if a.pileup:
+        line.update(pileup_phase(eng, lens, centres, queries, best, a))
     print(json.dumps(line))
     eng.close()
 
