@@ -403,6 +403,39 @@ int mc_nw_pileup_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, cons
 int mc_nw_pileup_profile(mc_ctx *ctx, double *out /* 3 */, int reset);
 
 /*
+ * THE PILE-UP WEIGHED BY BASE QUALITY.  mc_load_qualities: a Phred value (0 .. MC_QUAL_MAX, a FASTQ
+ * byte - 33) per byte of the loaded sequences, qual[seq_off[i] + t] belonging to base t of point i
+ * as written (points without qualities, the centres, hold 0).  bytes must equal the loaded
+ * seq_off[n] and no value may exceed MC_QUAL_MAX (MC_ERR_ARG, the qualities loaded before stay);
+ * no sequences: MC_ERR_STATE.  A later mc_load_sequences / mc_load_packed drops the qualities.
+ * mc_nw_qpileup_strands: mc_nw_pileup_strands -- the pairs, the operand rule, the batching and its
+ * environment caps, the errors, row_off, score / len / ids and the count table are that call's, bit
+ * for bit -- with a second table of the same shape, wtable, that receives weights.  Qs(i), the
+ * quality of base i of seq1 as aligned, is the read's quality at i on plus and at la - 1 - i on
+ * minus.  Walking the alignment with i read bases and j centre bases consumed:
+ *   '=' or 'X'   wtable row j, the channel of the read's byte += Qs(i); i++, j++
+ *   a 'D' run of n   every one of its n rows, channel 5 += min(Qs(i - 1) if i > 0, Qs(i) if i < la)
+ *                (0 if neither exists); j += n
+ *   an 'I' run of n   row j, channel 6 += min Qs(i .. i + n - 1); i += n
+ * Channel 7 is reserved and stays 0.  The weights are integer sums: wtable does not depend on the
+ * order of the pairs or on the batches; with every quality 1 (and no empty read), wtable's
+ * channels 0 .. 6 equal table's.
+ * table and wtable both NULL: the offsets only.  Exactly one of them NULL: MC_ERR_ARG.  No
+ * qualities loaded: MC_ERR_STATE.  Weights are uint32_t: a target that receives more than
+ * (2^32 - 1) / MC_QUAL_MAX = 46,182,038 pairs is MC_ERR_ARG.  These are found before any launch and
+ * write nothing.
+ * Device: a kernel of its own beside mc_nw_pileup_strands' (which that call keeps launching): the
+ * counts go the same way; the weights take an atomic per column -- a lane walks a run of at most 8
+ * columns, longer runs are taken by the whole wave, 64 consecutive columns per step.
+ */
+#define MC_QUAL_MAX 93
+int mc_load_qualities(mc_ctx *ctx, const uint8_t *qual, uint64_t bytes);
+int mc_nw_qpileup_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                          const uint32_t *targets, uint32_t nt, uint64_t *row_off /* nt + 1, required */,
+                          uint32_t *table, uint32_t *wtable /* each row_off[nt] * MC_PILEUP_CH */, uint64_t cap_rows,
+                          int32_t *score, int32_t *len, int32_t *ids /* m each, may be NULL */);
+
+/*
  * Accumulation (ClusterFactory::accumulate, ClusterFactory.cpp:637-714).
  * The bvec of Runner.cpp:342-350 is only ever shrunk after insert_finalize, so the device
  * holds one static candidate order (bin-major, length-sorted within bins) plus an alive

@@ -34,6 +34,7 @@ ERR_ARG, ERR_UNSUPPORTED = 1, 6
 ERR_STATE = 3
 CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # MC_CIGAR_*: mc_nw_align_strands' words are run << 4 | op
 PILEUP_CH = 8  # MC_PILEUP_CH: counters per row of mc_nw_pileup_strands' table
+QUAL_MAX = 93  # MC_QUAL_MAX: the largest Phred value mc_load_qualities takes
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
 
@@ -121,6 +122,11 @@ def gpu_lib():
         lib.mc_nw_pileup_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mc_nw_pileup_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.mc_load_qualities.restype = C.c_int
+        lib.mc_load_qualities.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.mc_nw_qpileup_strands.restype = C.c_int
+        lib.mc_nw_qpileup_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         _bind_steps(lib)
         _gpu = lib
     return _gpu
@@ -164,6 +170,10 @@ def host_lib():
         lib = C.CDLL(HOST_LIB)
         lib.mcl_parse.restype = C.c_void_p
         lib.mcl_parse.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_char_p, C.c_int]
+        lib.mcl_parse_q.restype = C.c_void_p
+        lib.mcl_parse_q.argtypes = lib.mcl_parse.argtypes
+        lib.mcl_qualities.restype = None
+        lib.mcl_qualities.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         lib.mcl_num_seqs.restype = C.c_uint64
         lib.mcl_num_seqs.argtypes = [C.c_void_p]
         lib.mcl_view.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4
@@ -198,6 +208,10 @@ def host_lib():
         lib.mcl_assign_consensus.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                              C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
                                              C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+        lib.mcl_assign_qconsensus.restype = C.c_int
+        lib.mcl_assign_qconsensus.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                              C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
+                                              C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -599,6 +613,37 @@ class Engine:
                                              _p(tab), C.c_uint64(rows), _p(sc), _p(ln), _p(ids)), "mc_nw_pileup_strands")
         return tab, off, sc, ln, ids
 
+    def load_qualities(self, q):
+        """mc_load_qualities: a Phred value (0 .. QUAL_MAX) per byte of the loaded sequences, at their
+        offsets; the next load of sequences drops them."""
+        q = np.ascontiguousarray(q, np.uint8)
+        self._ck(self.lib.mc_load_qualities(self.ctx, _p(q), C.c_uint64(len(q))), "mc_load_qualities")
+
+    def nw_qpileup_strands(self, a, b, a_minus, targets):
+        """mc_nw_qpileup_strands: nw_pileup_strands with the loaded qualities summed beside the counts
+        -> (table[rows, 8], wtable[rows, 8], row_off, score, len, ids).  ``wtable``: per column the
+        qualities of the reads' bases by channel 0..4, channel 5 the deletions (the smaller quality
+        of the two read bases around the gap), 6 the insertions (the smallest quality of the inserted
+        bases), 7 zero; a minus pair's qualities run backwards."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        am = None if a_minus is None else np.ascontiguousarray(a_minus, np.uint8)
+        tg = np.ascontiguousarray(targets, np.uint32)
+        assert len(b) == len(a) and (am is None or len(am) == len(a))
+        m, nt = len(a), len(tg)
+        off = np.zeros(nt + 1, np.uint64)
+        sc = np.zeros(m, np.int32)
+        ln = np.zeros(m, np.int32)
+        ids = np.zeros(m, np.int32)
+        self._ck(self.lib.mc_nw_qpileup_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), _p(tg), C.c_uint32(nt), _p(off), None,
+                                              None, C.c_uint64(0), None, None, None), "mc_nw_qpileup_strands")
+        rows = int(off[-1])
+        tab = np.zeros((rows, PILEUP_CH), np.uint32)
+        wtab = np.zeros((rows, PILEUP_CH), np.uint32)
+        self._ck(self.lib.mc_nw_qpileup_strands(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), _p(tg), C.c_uint32(nt), _p(off),
+                                              _p(tab), _p(wtab), C.c_uint64(rows), _p(sc), _p(ln), _p(ids)), "mc_nw_qpileup_strands")
+        return tab, wtab, off, sc, ln, ids
+
     def nw_pileup_profile(self, reset=False):
         """mc_nw_pileup_profile -> (forward ms, traceback ms, pile-up ms) since the last reset."""
         out = np.zeros(3)
@@ -630,8 +675,8 @@ class Engine:
 
 
 def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None,
-                 identity=False, min_identity=None, paf=None, consensus=None, pileup=None):
-    """Place the reads of the FASTA file(s) ``reads`` into the clustering saved by
+                 identity=False, min_identity=None, paf=None, consensus=None, pileup=None, quality=False):
+    """Place the reads of the FASTA or FASTQ file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
     similar centres) and, if given, the unassigned reads as FASTA; returns the stats dict.
@@ -653,13 +698,22 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     either implies ``identity``): every assigned read is piled up on its centre (mc_nw_pileup_strands);
     ``consensus`` gets every centre's consensus as FASTA, ``pileup`` the per-column counts of the centres
     with reads; the stats gain ``consensus_pairs``, ``consensus_centres``, ``consensus_passes``,
-    ``realigned_centres`` and ``insertion_sites``."""
+    ``realigned_centres`` and ``insertion_sites``.
+    ``quality``: meshclust-assign's --quality (mcl_assign_qconsensus; with ``consensus`` and/or ``pileup``, every
+    reads file FASTQ): the pile-up is weighed by base quality (mc_nw_qpileup_strands), ``consensus`` is written
+    as FASTQ with a quality per base, the ``pileup`` rows gain wA wC wG wT wN wdel, the stats ``quality``."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    if consensus is not None or pileup is not None:
+    if quality:
+        rc = lib.mcl_assign_qconsensus(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                       unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
+                                       hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),
+                                       paf.encode() if paf else None, consensus.encode() if consensus else None,
+                                       pileup.encode() if pileup else None, 1, buf, len(buf))
+    elif consensus is not None or pileup is not None:
         rc = lib.mcl_assign_consensus(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                       unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
                                       hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),
@@ -692,16 +746,28 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
 
 
 class Dataset:
-    """Parsed FASTA held by libmeshclust (one parse, many GPU runs)."""
+    """Parsed FASTA / FASTQ files held by libmeshclust (one parse, many GPU runs).  A file whose
+    first non-empty line starts with '@' is FASTQ; ``qualities=True`` (mcl_parse_q) keeps its
+    qualities for ``qualities()``."""
 
-    def __init__(self, files, threads=8):
+    def __init__(self, files, threads=8, qualities=False):
         self.lib = host_lib()
+        self.h = None
         arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
         err = C.create_string_buffer(1024)
-        self.h = self.lib.mcl_parse(arr, len(files), threads, err, 1024)
+        self.h = (self.lib.mcl_parse_q if qualities else self.lib.mcl_parse)(arr, len(files), threads, err, 1024)
         if not self.h:
             raise MCError("parse failed: " + err.value.decode())
         self.n = self.lib.mcl_num_seqs(self.h)
+
+    def qualities(self):
+        """mcl_qualities -> the Phred values (uint8, 0..93), one per expanded byte at seq_off (0 for
+        the records of FASTA files); None if the dataset was parsed without ``qualities=True``."""
+        q, n = C.c_void_p(), C.c_uint64()
+        self.lib.mcl_qualities(self.h, C.byref(q), C.byref(n))
+        if not q.value:
+            return None
+        return np.ctypeslib.as_array(C.cast(q, C.POINTER(C.c_uint8)), shape=(n.value,)).copy()
 
     def records(self):
         """[(header, codes uint8, [[start, end], ...])] as parsed (ChromListMaker +

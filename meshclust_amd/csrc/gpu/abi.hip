@@ -300,7 +300,7 @@ int mc_ctx_destroy(mc_ctx *c) {
                  &c->s_c, &c->s_d, &c->s_e, &c->s_f, &c->s_g, &c->s_h, &c->s_i, &c->s_j, &c->s_k, &c->hs, &c->mag_s, &c->sumsq_s, &c->len_s, &c->ticket,
                  &c->msum, &c->ident_s, &c->al_a, &c->al_b, &c->al_out, &c->al_id, &c->ord_ids, &c->acc_out, &c->sp_words, &c->sp_keys,
                  &c->sp_scr, &c->sp_nodes, &c->sp_nn, &c->sp_q, &c->sp_err, &c->u_off, &c->u_mem, &c->nw_items, &c->nw_gran, &c->rc_seq, &c->tr_choice, &c->tr_bnd, &c->tr_ops, &c->tr_pairs, &c->tr_res, &c->tr_idx, &c->tr_dst,
-                 &c->tr_out, &c->tr_err, &c->pu_table, &c->pu_diff, &c->pu_rows, &c->pu_toff, &c->pu_roff})
+                 &c->tr_out, &c->tr_err, &c->pu_table, &c->pu_diff, &c->pu_rows, &c->pu_toff, &c->pu_roff, &c->qual, &c->pu_wtable, &c->pu_qoff})
     release(*b);
   if (c->h_scan) (void)hipHostFree(c->h_scan);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -347,6 +347,7 @@ int mc_load_sequences(mc_ctx *c, const uint8_t *codes, const uint64_t *seq_off, 
   if (c) {
     c->h_uoff.clear();
     c->h_umem.clear();
+    c->has_qual = false;  // (mc_load_qualities' values belonged to the sequences replaced here)
   }
   if (!c || !seq_off || !seg_off || (n && !codes)) return MC_ERR_ARG;
   std::vector<uint64_t> pk_off;
@@ -364,6 +365,7 @@ int mc_load_packed(mc_ctx *c, const uint32_t *packed, const uint64_t *pk_off, co
   if (c) {
     c->h_uoff.clear();
     c->h_umem.clear();
+    c->has_qual = false;  // (mc_load_qualities' values belonged to the sequences replaced here)
   }
   if (!c || !pk_off || !seq_off || !seg_off || (n && !packed) || (nexc && (!exc_pos || !exc_val))) return MC_ERR_ARG;
   for (uint64_t i = 0; i < n; i++)
@@ -1069,11 +1071,21 @@ int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const u
   return MC_OK;
 }
 
-int mc_nw_pileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
-                         const uint32_t *targets, uint32_t nt, uint64_t *row_off, uint32_t *table, uint64_t cap_rows,
-                         int32_t *score, int32_t *len, int32_t *ids) {
+// mc_nw_pileup_strands (weighted false, wtable NULL) and mc_nw_qpileup_strands (weighted: the
+// same call with nwt_qpileup_kernel in place of nwt_pileup_kernel and a second table)
+static int pileup_call(mc_ctx *c, const std::string &who, bool weighted, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus,
+                       uint64_t m, const uint32_t *targets, uint32_t nt, uint64_t *row_off, uint32_t *table, uint32_t *wtable,
+                       uint64_t cap_rows, int32_t *score, int32_t *len, int32_t *ids) {
   if (!c || !c->codes.p) return MC_ERR_STATE;
+  if (weighted && !c->has_qual) {
+    set_error(who + ": no qualities are loaded (mc_load_qualities)");
+    return MC_ERR_STATE;
+  }
   if (!row_off || (nt && !targets) || (m && (!a || !b))) return MC_ERR_ARG;
+  if (weighted && !table != !wtable) {
+    set_error(who + ": table and wtable are given together (both NULL: the offsets only)");
+    return MC_ERR_ARG;
+  }
   MCG_CHECK(hipSetDevice(c->device));
   TRY(check_ids(c, targets, nt));
   TRY(check_ids(c, a, m));
@@ -1082,18 +1094,27 @@ int mc_nw_pileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const 
   std::vector<uint32_t> tindex(c->n, NO_TARGET);  // point id -> its place among the targets
   for (uint32_t t = 0; t < nt; t++) {
     if (tindex[targets[t]] != NO_TARGET) {
-      set_error("mc_nw_pileup_strands: point " + std::to_string(targets[t]) + " is listed twice among the targets");
+      set_error(who + ": point " + std::to_string(targets[t]) + " is listed twice among the targets");
       return MC_ERR_ARG;
     }
     tindex[targets[t]] = t;
   }
   for (uint64_t i = 0; i < m; i++)
     if (tindex[b[i]] == NO_TARGET) {
-      set_error("mc_nw_pileup_strands: pair " + std::to_string(i) + "'s seq2, point " + std::to_string(b[i]) +
+      set_error(who + ": pair " + std::to_string(i) + "'s seq2, point " + std::to_string(b[i]) +
                 ", is not among the targets");
       return MC_ERR_ARG;
     }
-  TRY(align_check_caps(c, "mc_nw_pileup_strands", a, b, m));
+  if (weighted) {  // a column's weight is at most MC_QUAL_MAX per pair: the sums must fit 32 bits
+    std::vector<uint64_t> npairs(nt, 0);
+    for (uint64_t i = 0; i < m; i++)
+      if (++npairs[tindex[b[i]]] > 0xffffffffull / MC_QUAL_MAX) {
+        set_error(who + ": target " + std::to_string(b[i]) + " receives more than " + std::to_string(0xffffffffull / MC_QUAL_MAX) +
+                  " pairs, its weights would not fit 32 bits");
+        return MC_ERR_ARG;
+      }
+  }
+  TRY(align_check_caps(c, who.c_str(), a, b, m));
   std::vector<uint64_t> toff(nt);
   row_off[0] = 0;
   for (uint32_t t = 0; t < nt; t++) {
@@ -1103,12 +1124,13 @@ int mc_nw_pileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const 
   if (!table) return MC_OK;
   const uint64_t rows = row_off[nt];
   if (cap_rows < rows) {
-    set_error("mc_nw_pileup_strands: table holds " + std::to_string(cap_rows) + " rows, the targets have " + std::to_string(rows));
+    set_error(who + ": table holds " + std::to_string(cap_rows) + " rows, the targets have " + std::to_string(rows));
     return MC_ERR_ARG;
   }
   if (rows == 0) return MC_OK;
   if (m == 0) {
     memset(table, 0, rows * MC_PILEUP_CH * 4);
+    if (weighted) memset(wtable, 0, rows * MC_PILEUP_CH * 4);
     return MC_OK;
   }
   // the table and the two difference arrays stay on the device for the whole call: zeroed once,
@@ -1119,10 +1141,16 @@ int mc_nw_pileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const 
   int32_t *d_deq = (int32_t *)c->pu_diff.p, *d_ddel = d_deq + rows;
   MCG_CHECK(hipMemsetAsync(d_table, 0, rows * MC_PILEUP_CH * 4, c->stream));
   MCG_CHECK(hipMemsetAsync(d_deq, 0, rows * 8, c->stream));
+  uint32_t *d_wtable = nullptr;
+  if (weighted) {
+    TRY(ensure(c->pu_wtable, rows * MC_PILEUP_CH * 4 + 64));
+    d_wtable = (uint32_t *)c->pu_wtable.p;
+    MCG_CHECK(hipMemsetAsync(d_wtable, 0, rows * MC_PILEUP_CH * 4, c->stream));
+  }
   const char *nv = getenv("MC_PILEUP_NAIVE");  // (a measurement aid: an atomic per column; the same table)
   const bool naive = nv && atoi(nv) != 0;
-  std::vector<uint64_t> rowbase;
-  TRY(align_batches(c, "mc_nw_pileup_strands", a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
+  std::vector<uint64_t> rowbase, qoff;
+  TRY(align_batches(c, who.c_str(), a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
     rowbase.resize(mb);
     for (uint64_t k = 0; k < mb; k++) {
       rowbase[k] = row_off[tindex[b[i0 + k]]];
@@ -1131,6 +1159,14 @@ int mc_nw_pileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const 
       if (ids) ids[i0 + k] = res[k * TRACE_RES + 2];
     }
     TRY(upload(c, c->pu_rows, rowbase.data(), mb, c->stream));
+    if (weighted) {
+      qoff.resize(mb);
+      for (uint64_t k = 0; k < mb; k++) qoff[k] = c->h_seq_off[a[i0 + k]];
+      TRY(upload(c, c->pu_qoff, qoff.data(), mb, c->stream));
+      return launch_nw_qpileup(c, (uint32_t)mb, (const TracePair *)c->tr_pairs.p, (const uint8_t *)c->rc_seq.p,
+                               (const uint32_t *)c->tr_ops.p, (const int32_t *)c->tr_res.p, (const uint64_t *)c->pu_rows.p,
+                               (const uint64_t *)c->pu_qoff.p, d_table, d_wtable, d_deq, d_ddel);
+    }
     return launch_nw_pileup(c, (uint32_t)mb, (const TracePair *)c->tr_pairs.p, (const uint8_t *)c->rc_seq.p,
                             (const uint32_t *)c->tr_ops.p, (const int32_t *)c->tr_res.p, (const uint64_t *)c->pu_rows.p, d_table,
                             d_deq, d_ddel, naive);
@@ -1139,8 +1175,44 @@ int mc_nw_pileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const 
   TRY(upload(c, c->pu_roff, row_off, (size_t)nt + 1, c->stream));
   TRY(launch_nw_pileup_finish(c, nt, (const uint64_t *)c->pu_toff.p, (const uint64_t *)c->pu_roff.p, d_table, d_deq, d_ddel));
   MCG_CHECK(hipMemcpyAsync(table, d_table, rows * MC_PILEUP_CH * 4, hipMemcpyDeviceToHost, c->stream));
+  if (weighted) MCG_CHECK(hipMemcpyAsync(wtable, d_wtable, rows * MC_PILEUP_CH * 4, hipMemcpyDeviceToHost, c->stream));
   MCG_CHECK(hipStreamSynchronize(c->stream));
   flush_timers(c);
+  return MC_OK;
+}
+
+int mc_nw_pileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                         const uint32_t *targets, uint32_t nt, uint64_t *row_off, uint32_t *table, uint64_t cap_rows,
+                         int32_t *score, int32_t *len, int32_t *ids) {
+  return pileup_call(c, "mc_nw_pileup_strands", false, a, b, a_minus, m, targets, nt, row_off, table, nullptr, cap_rows, score, len,
+                     ids);
+}
+
+int mc_nw_qpileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                          const uint32_t *targets, uint32_t nt, uint64_t *row_off, uint32_t *table, uint32_t *wtable,
+                          uint64_t cap_rows, int32_t *score, int32_t *len, int32_t *ids) {
+  return pileup_call(c, "mc_nw_qpileup_strands", true, a, b, a_minus, m, targets, nt, row_off, table, wtable, cap_rows, score, len,
+                     ids);
+}
+
+// A Phred value (0 .. MC_QUAL_MAX) per byte of the loaded sequences, at their offsets.
+int mc_load_qualities(mc_ctx *c, const uint8_t *qual, uint64_t bytes) {
+  if (!c || !c->codes.p) return MC_ERR_STATE;
+  const uint64_t want = c->h_seq_off.empty() ? 0 : c->h_seq_off.back();
+  if (bytes != want || (bytes && !qual)) {
+    set_error("mc_load_qualities: " + std::to_string(bytes) + " values, the loaded sequences have " + std::to_string(want) + " bytes");
+    return MC_ERR_ARG;
+  }
+  for (uint64_t i = 0; i < bytes; i++)
+    if (qual[i] > MC_QUAL_MAX) {
+      set_error("mc_load_qualities: value " + std::to_string((int)qual[i]) + " at byte " + std::to_string(i) + " is above MC_QUAL_MAX");
+      return MC_ERR_ARG;
+    }
+  MCG_CHECK(hipSetDevice(c->device));
+  TRY(ensure(c->qual, bytes + 64));
+  if (bytes) MCG_CHECK(hipMemcpyAsync(c->qual.p, qual, bytes, hipMemcpyHostToDevice, c->stream));
+  MCG_CHECK(hipStreamSynchronize(c->stream));
+  c->has_qual = true;
   return MC_OK;
 }
 

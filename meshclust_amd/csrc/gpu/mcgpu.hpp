@@ -181,6 +181,10 @@ struct mc_ctx {
   // ('=' and 'D' coverage, an int per row), a batch's row base per pair, the targets' code offsets
   // and row offsets
   mcg::Buf pu_table, pu_diff, pu_rows, pu_toff, pu_roff;
+  // mc_load_qualities: a Phred value per loaded byte (dropped by the next load of sequences);
+  // mc_nw_qpileup_strands: the call's weight table and a batch's read offset per pair
+  mcg::Buf qual, pu_wtable, pu_qoff;
+  bool has_qual = false;
   // mc_update_iteration's member lists on the device and their host shadow: re-uploaded only
   // when a merge changed them (cleared when sequences are loaded: the ids were checked against n)
   mcg::Buf u_off, u_mem;
@@ -287,6 +291,11 @@ int launch_nw_pileup(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint
                      bool naive);
 int launch_nw_pileup_finish(mc_ctx *c, uint32_t nt, const uint64_t *d_tgt_off, const uint64_t *d_row_off, uint32_t *d_table,
                             const int32_t *d_deq, const int32_t *d_ddel);
+// the same counts and, beside them, the loaded qualities (c->qual) summed per column into d_wtable
+// (mc_nw_qpileup_strands); d_qoff[p]: the offset of pair p's read in the loaded sequences
+int launch_nw_qpileup(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint8_t *d_rc, const uint32_t *d_ops,
+                      const int32_t *d_res, const uint64_t *d_rowbase, const uint64_t *d_qoff, uint32_t *d_table,
+                      uint32_t *d_wtable, int32_t *d_deq, int32_t *d_ddel);
 
 }  // namespace mcg
 

@@ -26,7 +26,7 @@ namespace mc {
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
     "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--consensus FILE] "
-    "[--pileup FILE] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
+    "[--pileup FILE] [--quality] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
     "  --top K --hits FILE  (given together, K = 1..8) also write the K best similar centres of every read to\n"
     "                  FILE: read, rank, centre, cluster index, combo 0 (and the strand with --both-strands)\n"
@@ -40,7 +40,12 @@ static const char *kUsage =
     "                  consensus as FASTA: >NAME depth=D sub=S del=X ins=I (a centre without reads: its own sequence)\n"
     "  --pileup FILE   (implies the --consensus pass) the counts behind it, for centres with reads: centre, column\n"
     "                  (the row after the last base: L+1, base *), centre base, depth, A, C, G, T, N, del, ins_reads,\n"
-    "                  ins_bases\n";
+    "                  ins_bases\n"
+    "  --quality       (with --consensus and/or --pileup; every reads file FASTQ) weigh the pile-up by base quality:\n"
+    "                  a column goes to the channel of the largest summed Phred value, the consensus is written as\n"
+    "                  FASTQ (@NAME depth=D sub=S del=X ins=I) with a quality per base, the pile-up rows gain wA wC wG\n"
+    "                  wT wN wdel\n"
+    "  reads and centres may be FASTA or FASTQ files (decided per file); without --quality the qualities are skipped\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
   AssignOptions o;
@@ -80,6 +85,8 @@ AssignOptions parse_assign_options(int argc, char **argv) {
     } else if (arg == "--pileup" && has) {
       o.pileup = argv[++i];
       o.identity = true;
+    } else if (arg == "--quality") {
+      o.quality = true;
     } else {
       struct stat st;
       if (stat(argv[i], &st) == 0 && S_ISREG(st.st_mode)) o.reads.push_back(argv[i]);
@@ -89,6 +96,8 @@ AssignOptions parse_assign_options(int argc, char **argv) {
   if (o.model.empty() || o.centres.empty() || o.reads.empty())
     throw Error(std::string("--model, --centres and at least one reads file are required\n") + kUsage, 1);
   if ((o.top > 0) != !o.hits.empty()) throw Error(std::string("--top K and --hits FILE are given together\n") + kUsage, 1);
+  if (o.quality && o.consensus.empty() && o.pileup.empty())
+    throw Error(std::string("--quality needs --consensus FILE and/or --pileup FILE\n") + kUsage, 1);
   return o;
 }
 
@@ -170,6 +179,8 @@ static std::vector<uint8_t> expanded_bytes(const Dataset &ds, uint32_t id) {
 // --consensus / --pileup: the pairs (read pa, centre pb < C, strand pm) piled up on the centres
 // 0 .. C-1 in one mc_nw_pileup_strands call; pid (if given) receives every pair's ids / len.
 // Centres with an insertion site have their pairs aligned again for the inserted bases.
+// opt.quality: mc_nw_qpileup_strands and consensus.hpp's weighted consensus over ds.qual instead;
+// the consensus is then FASTQ and every pile-up row gains the weights of channels 0..5.
 static void pileup_outputs(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::vector<uint32_t> &pa,
                            const std::vector<uint32_t> &pb, const std::vector<uint8_t> &pm, const AssignOptions &opt,
                            AssignResult &r, std::vector<double> *pid) {
@@ -181,11 +192,16 @@ static void pileup_outputs(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std
     targets[j] = j;
     rows += ds.lengths[j] + 1;
   }
-  std::vector<uint32_t> table(rows * MC_PILEUP_CH);
+  std::vector<uint32_t> table(rows * MC_PILEUP_CH), wtable(opt.quality ? rows * MC_PILEUP_CH : 0);
   std::vector<int32_t> ln(m), idn(m);
-  check(mc_nw_pileup_strands(ctx, pa.data(), pb.data(), pm.data(), m, targets.data(), C, row_off.data(), table.data(), rows,
-                             nullptr, ln.data(), idn.data()),
-        "mc_nw_pileup_strands");
+  if (opt.quality)
+    check(mc_nw_qpileup_strands(ctx, pa.data(), pb.data(), pm.data(), m, targets.data(), C, row_off.data(), table.data(),
+                                wtable.data(), rows, nullptr, ln.data(), idn.data()),
+          "mc_nw_qpileup_strands");
+  else
+    check(mc_nw_pileup_strands(ctx, pa.data(), pb.data(), pm.data(), m, targets.data(), C, row_off.data(), table.data(), rows,
+                               nullptr, ln.data(), idn.data()),
+          "mc_nw_pileup_strands");
   if (pid)
     for (size_t p = 0; p < m; p++) (*pid)[p] = (double)idn[p] / (double)ln[p];
   r.consensus = true;
@@ -202,13 +218,15 @@ static void pileup_outputs(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std
   std::string fa, tsv;
   char num[160];
   std::vector<uint32_t> qa, qb, cig;
-  std::vector<uint8_t> qm, rcb;
+  std::vector<uint8_t> qm, rcb, rq;
   std::vector<uint64_t> off;
   for (uint32_t j = 0; j < C; j++) {
     const uint64_t L = ds.lengths[j], depth = from[j + 1] - from[j];
     const uint32_t *rw = table.data() + row_off[j] * MC_PILEUP_CH;
     const std::vector<uint8_t> cen = expanded_bytes(ds, j);
+    const uint32_t *ww = opt.quality ? wtable.data() + row_off[j] * MC_PILEUP_CH : nullptr;
     InsertionRuns runs;
+    QInsertionRuns qruns;
     if (depth > 0) {
       r.consensus_centres++;
       const std::vector<uint64_t> sites = insertion_sites(rw, L, depth);
@@ -234,27 +252,58 @@ static void pileup_outputs(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std
             revseq(rd.data(), rd.size(), rcb.data());
             rd.swap(rcb);
           }
-          insertion_runs(cig.data() + off[k], off[k + 1] - off[k], rd.data(), sites, runs);
+          if (opt.quality) {  // the read's qualities in the aligned string's order
+            rq.assign(ds.qual.begin() + ds.seq_off[qa[k]], ds.qual.begin() + ds.seq_off[qa[k] + 1]);
+            if (qm[k]) std::reverse(rq.begin(), rq.end());
+            qinsertion_runs(cig.data() + off[k], off[k + 1] - off[k], rd.data(), rq.data(), sites, qruns);
+          } else {
+            insertion_runs(cig.data() + off[k], off[k + 1] - off[k], rd.data(), sites, runs);
+          }
         }
       }
     }
-    const Consensus cs = consensus_of(cen.data(), L, rw, depth, runs);
+    Consensus cs;
+    std::string cq;  // --quality: the consensus's quality line
+    if (opt.quality) {
+      QConsensus q = qconsensus_of(cen.data(), L, rw, ww, depth, qruns);
+      cs.seq.swap(q.seq);
+      cq.swap(q.qual);
+      cs.sub = q.sub, cs.del = q.del, cs.ins = q.ins;
+    } else {
+      cs = consensus_of(cen.data(), L, rw, depth, runs);
+    }
     r.insertion_sites += cs.ins;
     if (!opt.consensus.empty()) {
-      fa.append(ds.headers[j]);
+      if (opt.quality) {
+        fa += '@';
+        fa.append(ds.headers[j].substr(1));
+      } else {
+        fa.append(ds.headers[j]);
+      }
       snprintf(num, sizeof num, " depth=%llu sub=%llu del=%llu ins=%llu\n", (unsigned long long)depth, (unsigned long long)cs.sub,
                (unsigned long long)cs.del, (unsigned long long)cs.ins);
       fa += num;
       fa += cs.seq;
       fa += '\n';
+      if (opt.quality) {
+        fa += "+\n";
+        fa += cq;
+        fa += '\n';
+      }
     }
     if (!opt.pileup.empty() && depth > 0)
       for (uint64_t t = 0; t <= L; t++) {
         const uint32_t *x = rw + t * MC_PILEUP_CH;
         tsv.append(ds.headers[j].substr(1));
-        snprintf(num, sizeof num, "\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", (unsigned long long)(t + 1),
+        snprintf(num, sizeof num, "\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u", (unsigned long long)(t + 1),
                  t < L ? pileup_base_char(cen[t]) : '*', (unsigned long long)depth, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7]);
         tsv += num;
+        if (opt.quality) {
+          const uint32_t *y = ww + t * MC_PILEUP_CH;
+          snprintf(num, sizeof num, "\t%u\t%u\t%u\t%u\t%u\t%u", y[0], y[1], y[2], y[3], y[4], y[5]);
+          tsv += num;
+        }
+        tsv += '\n';
       }
   }
   if (!opt.consensus.empty()) write_text(opt.consensus, fa);
@@ -288,7 +337,10 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   std::vector<std::string> files{opt.centres};
   files.insert(files.end(), opt.reads.begin(), opt.reads.end());
   Dataset ds;
-  parse_fasta_files(files, ds, threads);  // centres first: their ids are 0 .. C-1
+  parse_fasta_files(files, ds, threads, opt.quality);  // centres first: their ids are 0 .. C-1
+  if (opt.quality)
+    for (size_t f = 1; f < files.size(); f++)
+      if (!ds.file_fastq[f]) throw Error("meshclust-assign: --quality needs FASTQ reads, " + files[f] + " is FASTA", 2);
   r.parse_ms = ms_since(t0);
   const uint64_t C = ds.file_count.empty() ? 0 : ds.file_count[0];
   if (C != model.centres)
@@ -308,6 +360,10 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   check(mc_load_packed(ctx, ds.packed.data(), ds.pk_off.data(), ds.seq_off.data(), ds.size(), ds.exc_pos.data(),
                        ds.exc_val.data(), ds.exc_pos.size(), ds.seg.data(), ds.seg_off.data()),
         "mc_load_packed");
+  if (opt.quality) {
+    check(mc_load_qualities(ctx, ds.qual.data(), ds.bases()), "mc_load_qualities");
+    r.quality = true;
+  }
   r.upload_ms = ms_since(t0);
   t0 = std::chrono::steady_clock::now();
   uint64_t largest = 0;
@@ -577,9 +633,9 @@ std::string assign_stats_json(const AssignResult &r) {
     if (r.consensus)
       snprintf(s + n, sizeof s - n,
                "\"consensus_pairs\": %llu, \"consensus_centres\": %llu, \"consensus_passes\": %d, \"realigned_centres\": %llu, "
-               "\"insertion_sites\": %llu, ",
+               "\"insertion_sites\": %llu, %s",
                (unsigned long long)r.consensus_pairs, (unsigned long long)r.consensus_centres, r.consensus_passes,
-               (unsigned long long)r.realigned_centres, (unsigned long long)r.insertion_sites);
+               (unsigned long long)r.realigned_centres, (unsigned long long)r.insertion_sites, r.quality ? "\"quality\": 1, " : "");
     snprintf(idms, sizeof idms, "\"identity\": %.3f, ", r.identity_ms);
   }
   snprintf(b, sizeof b,

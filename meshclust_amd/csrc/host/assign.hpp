@@ -22,6 +22,7 @@ struct AssignOptions {
   std::string paf;            // --paf FILE (implies identity): the alignments of the reported pairs as PAF
   std::string consensus;      // --consensus FILE (implies identity): a consensus per centre from its assigned reads, FASTA
   std::string pileup;         // --pileup FILE (implies the consensus pass): the per-column counts behind it, TSV
+  bool quality = false;       // --quality (with consensus and/or pileup; FASTQ reads): the pile-up weighed by base quality
 };
 
 struct AssignResult {
@@ -42,6 +43,7 @@ struct AssignResult {
   uint64_t consensus_pairs = 0, consensus_centres = 0;  // (1: the pile-up gave the identities too; 2: it came second),
   int consensus_passes = 0;                             // centres re-aligned for their inserted bases, sites applied
   uint64_t realigned_centres = 0, insertion_sites = 0;
+  bool quality = false;          // --quality: the qualities were uploaded and the weighted pile-up ran
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
   double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0;
 };
@@ -76,6 +78,13 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // otherwise it is a second pass over the selected pairs ("consensus_passes" 1 or 2 in the stats).
 // Centres with an insertion site are re-aligned with mc_nw_align_strands for the inserted bases
 // ("realigned_centres").
+// Reads and centres may be FASTA or FASTQ files (fasta.hpp); the qualities are skipped unless
+// quality is set, which needs consensus and/or pileup (parse_assign_options: usage error) and every
+// reads file to be FASTQ (Error of code 2 naming the file).  The qualities are then uploaded
+// (mc_load_qualities), the pile-up pass goes through mc_nw_qpileup_strands, consensus is written as
+// FASTQ ("@NAME depth=D sub=S del=X ins=I", sequence, "+", a quality per base; consensus.hpp
+// qconsensus_of; a centre without reads: its own sequence at '!'), every pileup row gains the six
+// weights wA wC wG wT wN wdel, and the stats "quality": 1.
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
 std::string assign_stats_json(const AssignResult &r);
 int assign_main(int argc, char **argv);

@@ -9,16 +9,34 @@
 
 extern "C" {
 
-void *mcl_parse(const char *const *files, int nfiles, int threads, char *err, int errcap) {
+static void *parse_entry(const char *const *files, int nfiles, int threads, bool keep_qual, char *err, int errcap) {
+  auto ds = std::make_unique<mc::Dataset>();
   try {
-    auto *ds = new mc::Dataset();
     std::vector<std::string> f(files, files + nfiles);
-    mc::parse_fasta_files(f, *ds, threads > 0 ? threads : 1);
-    return ds;
+    mc::parse_fasta_files(f, *ds, threads > 0 ? threads : 1, keep_qual);
+    return ds.release();
   } catch (const std::exception &e) {
     if (err && errcap > 0) snprintf(err, errcap, "%s", e.what());
     return nullptr;
   }
+}
+
+// FASTA and FASTQ files (decided per file, fasta.hpp); FASTQ qualities are checked and skipped.
+void *mcl_parse(const char *const *files, int nfiles, int threads, char *err, int errcap) {
+  return parse_entry(files, nfiles, threads, false, err, errcap);
+}
+
+// mcl_parse with the FASTQ qualities kept (mcl_qualities).
+void *mcl_parse_q(const char *const *files, int nfiles, int threads, char *err, int errcap) {
+  return parse_entry(files, nfiles, threads, true, err, errcap);
+}
+
+// The Phred values of a dataset parsed by mcl_parse_q: q[seq_off[i] + t] belongs to base t of
+// record i (0 for the records of FASTA files), *n = seq_off[records].  After mcl_parse: *q NULL, *n 0.
+void mcl_qualities(void *dsv, const uint8_t **q, uint64_t *n) {
+  const auto *ds = (const mc::Dataset *)dsv;
+  *q = ds->qual.empty() ? nullptr : ds->qual.data();
+  *n = ds->qual.size();
 }
 
 uint64_t mcl_num_seqs(void *ds) { return ((mc::Dataset *)ds)->size(); }

@@ -17,9 +17,10 @@ extern "C" {
 static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
                         int threads, const char *tsv, const char *unassigned, bool both_strands, int top, const char *hits,
                         int identity, double min_identity, const char *paf, const char *consensus, const char *pileup,
-                        char *stats, int cap) {
+                        bool quality, char *stats, int cap) {
   try {
     mc::AssignOptions opt;
+    opt.quality = quality;
     if (paf) opt.paf = paf;
     if (consensus) opt.consensus = consensus;
     if (pileup) opt.pileup = pileup;
@@ -39,6 +40,8 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
     if (unassigned) opt.unassigned = unassigned;
     opt.quiet = true;
     if (opt.model.empty() || opt.centres.empty() || opt.reads.empty()) throw mc::Error("mcl_assign: model, centres and reads are required", 1);
+    if (quality && opt.consensus.empty() && opt.pileup.empty())
+      throw mc::Error("mcl_assign_qconsensus: quality needs consensus and/or pileup", 1);
     const mc::AssignResult r = mc::run_assign(ctx, opt);
     if (stats && cap > 0) snprintf(stats, cap, "%s", mc::assign_stats_json(r).c_str());
     return 0;
@@ -56,7 +59,7 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
 
 int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
                const char *tsv, const char *unassigned, char *stats, int cap) {
-  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, false, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, stats, cap);
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, false, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign with meshclust-assign's --both-strands when both_strands is non-zero (mc_assign_strands
@@ -64,7 +67,7 @@ int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *
 // Where only the pair list applies it returns 2 with the reason in stats.
 int mcl_assign_strands(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
                        int threads, const char *tsv, const char *unassigned, int both_strands, char *stats, int cap) {
-  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, stats, cap);
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign_strands with meshclust-assign's --top `top` --hits `hits` (mc_assign_top): the TSV is
@@ -74,7 +77,7 @@ int mcl_assign_top(mc_ctx *ctx, const char *model, const char *centres, const ch
                    const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, char *stats,
                    int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, 0, -1.0, nullptr, nullptr,
-                      nullptr, stats, cap);
+                      nullptr, false, stats, cap);
 }
 
 // mcl_assign_top with meshclust-assign's --identity (identity non-zero) and --min-identity
@@ -85,7 +88,7 @@ int mcl_assign_identity(mc_ctx *ctx, const char *model, const char *centres, con
                         const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
                         double min_identity, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, nullptr, nullptr, nullptr, stats, cap);
+                      min_identity, nullptr, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign_identity with meshclust-assign's --paf `paf` (mc_nw_align_strands; implies identity):
@@ -95,7 +98,7 @@ int mcl_assign_paf(mc_ctx *ctx, const char *model, const char *centres, const ch
                    const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
                    double min_identity, const char *paf, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, paf, nullptr, nullptr, stats, cap);
+                      min_identity, paf, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign_paf with meshclust-assign's --consensus `consensus` and --pileup `pileup`
@@ -107,7 +110,19 @@ int mcl_assign_consensus(mc_ctx *ctx, const char *model, const char *centres, co
                          const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
                          double min_identity, const char *paf, const char *consensus, const char *pileup, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, paf, consensus, pileup, stats, cap);
+                      min_identity, paf, consensus, pileup, false, stats, cap);
+}
+
+// mcl_assign_consensus with meshclust-assign's --quality when quality is non-zero (mc_load_qualities,
+// mc_nw_qpileup_strands): it needs consensus and/or pileup and FASTQ reads; the consensus is written
+// as FASTQ with a quality per base, the pile-up rows gain the six weights, the summary "quality": 1.
+// quality = 0 is mcl_assign_consensus.
+int mcl_assign_qconsensus(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
+                          const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
+                          double min_identity, const char *paf, const char *consensus, const char *pileup, int quality,
+                          char *stats, int cap) {
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
+                      min_identity, paf, consensus, pileup, quality != 0, stats, cap);
 }
 
 // Records ids[0..n) of a parsed dataset (mcl_parse) as FASTA: header lines unchanged, each

@@ -4,6 +4,10 @@
 // at the start of a line), each thread splits its chunk into records with safe_getline's
 // line semantics, runs Chromosome::help + encodeNucleotides on every record in place and
 // packs the codes; the chunks are then stitched together with prefix sums.
+//
+// A FASTQ file (its first non-empty line starts with '@') is read whole instead: a '@' at a line
+// start may be a quality line, so a serial pre-pass over the four-line records lists the record
+// starts (fq_index), and the threads then parse ranges of records into the same chunks.
 #include "fasta.hpp"
 
 #include <fcntl.h>
@@ -150,6 +154,7 @@ struct Chunk {
   std::vector<uint64_t> nseg;     // segment pairs per record
   std::vector<uint64_t> exc_pos;  // chunk-local byte positions
   std::vector<uint8_t> exc_val;
+  std::vector<uint8_t> qual;  // FASTQ with qualities kept: Phred values at the chunk-local bytes
   uint64_t bytes = 0;
   std::string err;
 };
@@ -257,6 +262,37 @@ inline void plain_segments(int64_t L, std::vector<int32_t> &seg) {
   }
 }
 
+// A record's gathered bytes `tmp` appended to the chunk: a plain record (A/C/G/T only, at least 20
+// bases: one N-free segment) is packed by encode_plain, any other goes through process_record in
+// place and keeps its bytes outside 0..3 as exceptions.
+void pack_record(Chunk &ck, Chunk::Rec &r, std::vector<uint8_t> &tmp, std::vector<int32_t> &segs) {
+  r.off = ck.bytes;
+  r.len = tmp.size();
+  ck.bytes += r.len;
+  if (r.len >= 20 && encode_plain(tmp.data(), tmp.size(), ck.pk)) {
+    const size_t s0 = ck.seg.size();
+    plain_segments((int64_t)r.len, ck.seg);
+    ck.nseg.push_back((ck.seg.size() - s0) / 2);
+    return;
+  }
+  if (!r.ready) throw Error("The header and the sequence must be set before calling finalize", 1);
+  process_record(tmp.data(), tmp.size(), segs);
+  ck.seg.insert(ck.seg.end(), segs.begin(), segs.end());
+  ck.nseg.push_back(segs.size() / 2);
+  for (size_t j = 0; j < tmp.size(); j += 16) {
+    uint32_t x = 0;
+    for (size_t t = 0; t < 16 && j + t < tmp.size(); t++) {
+      const uint8_t c = tmp[j + t];
+      x |= (uint32_t)(c & 3) << (2 * t);
+      if (c > 3) {
+        ck.exc_pos.push_back(r.off + j + t);
+        ck.exc_val.push_back(c);
+      }
+    }
+    ck.pk.push_back(x);
+  }
+}
+
 // Records of buf[a, z): a line starting with '>' opens a record whose header is the whole
 // line; other lines are appended to the current record.  `eof`: the chunk ends the file (the
 // final empty read sets isBaseReady of the last record).  A record's lines are gathered, then
@@ -269,32 +305,7 @@ void parse_chunk(const char *buf, size_t a, size_t z, bool first, bool eof, cons
   std::vector<int32_t> segs;
   auto close = [&]() {
     if (!cur) return;
-    auto &r = *cur;
-    r.off = ck.bytes;
-    r.len = tmp.size();
-    ck.bytes += r.len;
-    if (r.len >= 20 && encode_plain(tmp.data(), tmp.size(), ck.pk)) {
-      const size_t s0 = ck.seg.size();
-      plain_segments((int64_t)r.len, ck.seg);
-      ck.nseg.push_back((ck.seg.size() - s0) / 2);
-    } else {
-      if (!r.ready) throw Error("The header and the sequence must be set before calling finalize", 1);
-      process_record(tmp.data(), tmp.size(), segs);
-      ck.seg.insert(ck.seg.end(), segs.begin(), segs.end());
-      ck.nseg.push_back(segs.size() / 2);
-      for (size_t j = 0; j < tmp.size(); j += 16) {
-        uint32_t x = 0;
-        for (size_t t = 0; t < 16 && j + t < tmp.size(); t++) {
-          const uint8_t c = tmp[j + t];
-          x |= (uint32_t)(c & 3) << (2 * t);
-          if (c > 3) {
-            ck.exc_pos.push_back(r.off + j + t);
-            ck.exc_val.push_back(c);
-          }
-        }
-        ck.pk.push_back(x);
-      }
-    }
+    pack_record(ck, *cur, tmp, segs);
     tmp.clear();
     cur = nullptr;
   };
@@ -484,9 +495,101 @@ void parse_chunk_lf(const char *buf, size_t a, size_t z, bool first, bool eof, c
   ck.pk.resize(np);
 }
 
+// ---- FASTQ ----------------------------------------------------------------------------------
+// One line of buf[p, n): its start, its length without the "\n" or "\r\n" that ends it, and the
+// start of the next line.  False if p is the end of the file.
+struct FqLine {
+  size_t at = 0, len = 0, next = 0;
+};
+inline bool fq_line(const char *buf, size_t n, size_t p, FqLine &l) {
+  if (p >= n) return false;
+  const char *nl = (const char *)memchr(buf + p, '\n', n - p);
+  const size_t e = nl ? (size_t)(nl - buf) : n;
+  l.at = p;
+  l.len = e - p;
+  if (l.len && buf[e - 1] == '\r') l.len--;
+  l.next = nl ? e + 1 : n;
+  return true;
+}
+
+// The four lines of the record that starts at p (a strict four-line record) -> nullptr, or what is
+// wrong with it.
+struct FqRec {
+  FqLine hdr, seq, plus, qual;
+};
+inline const char *fq_record(const char *buf, size_t n, size_t p, FqRec &r) {
+  if (!fq_line(buf, n, p, r.hdr) || r.hdr.len == 0 || buf[p] != '@')
+    return "does not start with '@' (a sequence or quality that continues on a second line: multi-line FASTQ is not supported)";
+  if (!fq_line(buf, n, r.hdr.next, r.seq)) return "the file ends inside the record (after its header)";
+  if (!fq_line(buf, n, r.seq.next, r.plus)) return "the file ends inside the record (after its sequence)";
+  if (r.plus.len == 0 || buf[r.plus.at] != '+') {
+    bool letters = r.plus.len > 0;
+    for (size_t i = 0; i < r.plus.len; i++) letters = letters && isalpha((unsigned char)buf[r.plus.at + i]);
+    return letters ? "the sequence continues on a second line: multi-line FASTQ is not supported"
+                   : "the third line does not start with '+'";
+  }
+  if (!fq_line(buf, n, r.plus.next, r.qual)) return "the file ends inside the record (no quality line)";
+  if (r.qual.len != r.seq.len) return "the quality line's length differs from the sequence line's";
+  return nullptr;
+}
+
+inline std::string fq_where(const std::string &path, uint64_t rec, const std::string &what) {
+  return path + ": FASTQ record " + std::to_string(rec) + ": " + what;
+}
+
+// The serial pre-pass: the start of every record of buf[0, n), in order ('@' at a line start may
+// be a quality line, so record starts are only known by counting lines).  Empty lines between
+// records are skipped.  Stops at the first record fq_record refuses: err is then its message.
+void fq_index(const char *buf, size_t n, const std::string &path, std::vector<size_t> &starts, std::string &err) {
+  FqRec r;
+  for (size_t p = 0; p < n;) {
+    if (buf[p] == '\n' || (buf[p] == '\r' && p + 1 < n && buf[p + 1] == '\n')) {
+      p += buf[p] == '\n' ? 1 : 2;
+      continue;
+    }
+    if (const char *what = fq_record(buf, n, p, r)) {
+      err = fq_where(path, starts.size() + 1, what);
+      return;
+    }
+    starts.push_back(p);
+    p = r.qual.next;
+  }
+}
+
+// The records starts[r0, r1) of a FASTQ file into ck, as parse_chunk does a FASTA chunk's: the
+// header's '@' is rewritten to '>' in the buffer (the stitch copies the header line from there),
+// the sequence line is packed by pack_record, the quality bytes (33..126) become Phred values at
+// the record's bytes if `keep`.
+void parse_fastq_records(char *buf, size_t n, const std::vector<size_t> &starts, size_t r0, size_t r1, bool keep,
+                         const std::string &path, Chunk &ck) {
+  std::vector<uint8_t> tmp;
+  std::vector<int32_t> segs;
+  FqRec q;
+  ck.recs.reserve(r1 - r0);
+  for (size_t k = r0; k < r1; k++) {
+    fq_record(buf, n, starts[k], q);  // (accepted by fq_index)
+    buf[q.hdr.at] = '>';
+    const uint8_t *ql = (const uint8_t *)buf + q.qual.at;
+    for (size_t i = 0; i < q.qual.len; i++)
+      if (ql[i] < 33 || ql[i] > 126)
+        throw Error(fq_where(path, k + 1, "quality byte " + std::to_string((int)ql[i]) + " at base " + std::to_string(i + 1) +
+                                              " is outside 33 .. 126"), 1);
+    ck.recs.push_back({q.hdr.at, q.hdr.len, 0, 0, (uint64_t)ck.pk.size(), true});
+    tmp.assign(buf + q.seq.at, buf + q.seq.at + q.seq.len);
+    pack_record(ck, ck.recs.back(), tmp, segs);
+    // (process_record works in place, so a record's expanded bytes are its sequence line's)
+    if (ck.recs.back().len != q.qual.len) throw Error(fq_where(path, k + 1, "the expanded sequence and its qualities differ in length"), 1);
+    if (keep) {
+      const size_t at = ck.qual.size();
+      ck.qual.resize(at + q.qual.len);
+      for (size_t i = 0; i < q.qual.len; i++) ck.qual[at + i] = (uint8_t)(ql[i] - 33);
+    }
+  }
+}
+
 }  // namespace
 
-void parse_fasta_files(const std::vector<std::string> &files, Dataset &ds, int threads) {
+void parse_fasta_files(const std::vector<std::string> &files, Dataset &ds, int threads, bool keep_qual) {
   if (threads < 1) threads = 1;
   if (ds.seq_off.empty()) {
     ds.seq_off.push_back(0);
@@ -546,59 +649,96 @@ void parse_fasta_files(const std::vector<std::string> &files, Dataset &ds, int t
       return v < 1 ? 1 : v > 64 ? 64 : v;
     }();
     const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)threads * per_thread, n / (1 << 16) + 1));
-    std::vector<size_t> cut(T + 1, n);
-    cut[0] = 0;
+    // FASTQ or FASTA: the first byte of the first non-empty line
+    bool fastq = false;
+    for (size_t got = 0; got < n && !bad;) {
+      const size_t end = std::min(n, got + (1 << 16));
+      read_at(wbuf + got, got, end);
+      size_t i = got;
+      while (i < end && (buf[i] == '\n' || buf[i] == '\r')) i++;
+      if (i < end) {
+        fastq = buf[i] == '@';
+        break;
+      }
+      got = end;
+    }
+    std::vector<Chunk> ck(T);
+    std::string fq_err;  // the first record the FASTQ pre-pass refused (the records before it are parsed)
+    if (fastq) {
+      const size_t B = 1 << 22;  // the whole file, then the record index, then the records in T ranges
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
-    for (int t = 1; t < T; t++) {
-      // first '>' at the start of a line at or after n * t / T (the byte before it read too)
-      const size_t c0 = (size_t)((double)n * t / T);
-      std::vector<char> win;
-      size_t base = c0 - 1, got = 0, i = 1;  // window = file bytes [base, base + got)
-      cut[t] = n;
-      for (size_t want = 1 << 13; base + got < n; want *= 2) {
-        const size_t end = std::min(n, base + got + want);
-        win.resize(end - base);
-        read_at(win.data() + got, base + got, end);
-        if (bad) break;
-        got = end - base;
-        bool hit = false;
-        for (; i < got; i++)
-          if (win[i] == '>' && (win[i - 1] == '\n' || win[i - 1] == '\r')) {
-            hit = true;
-            break;
-          }
-        if (hit) {
-          cut[t] = base + i;
-          break;
+      for (size_t b = 0; b < (n + B - 1) / B; b++) read_at(wbuf + b * B, b * B, std::min(n, (b + 1) * B));
+      if (bad) {
+        close(fd);
+        throw Error("cannot read " + path, 1);
+      }
+      std::vector<size_t> starts;
+      fq_index(buf, n, path, starts, fq_err);
+      lap("index");
+      const size_t R = starts.size();
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
+      for (int t = 0; t < T; t++) {
+        try {
+          parse_fastq_records(wbuf, n, starts, R * t / T, R * (t + 1) / T, keep_qual, path, ck[t]);
+        } catch (const std::exception &e) {
+          ck[t].err = e.what();
         }
       }
-    }
-    if (bad) {
-      close(fd);
-      throw Error("cannot read " + path, 1);
-    }
-    lap("cut");
-    std::vector<Chunk> ck(T);
-    static const bool fast_lf = !getenv("MC_PARSE_LINES");  // (MC_PARSE_LINES=1: parse_chunk only)
+    } else {
+      std::vector<size_t> cut(T + 1, n);
+      cut[0] = 0;
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
-    for (int t = 0; t < T; t++) {
-      try {
-        if (cut[t] < cut[t + 1]) {
-          read_at(wbuf + cut[t], cut[t], cut[t + 1]);
-          if (bad) throw Error("cannot read " + path, 1);
-          if (fast_lf && !memchr(buf + cut[t], '\r', cut[t + 1] - cut[t]))
-            parse_chunk_lf(buf, cut[t], cut[t + 1], t == 0, cut[t + 1] == n, path, ck[t]);
-          else
-            parse_chunk(buf, cut[t], cut[t + 1], t == 0, cut[t + 1] == n, path, ck[t]);
+      for (int t = 1; t < T; t++) {
+        // first '>' at the start of a line at or after n * t / T (the byte before it read too)
+        const size_t c0 = (size_t)((double)n * t / T);
+        std::vector<char> win;
+        size_t base = c0 - 1, got = 0, i = 1;  // window = file bytes [base, base + got)
+        cut[t] = n;
+        for (size_t want = 1 << 13; base + got < n; want *= 2) {
+          const size_t end = std::min(n, base + got + want);
+          win.resize(end - base);
+          read_at(win.data() + got, base + got, end);
+          if (bad) break;
+          got = end - base;
+          bool hit = false;
+          for (; i < got; i++)
+            if (win[i] == '>' && (win[i - 1] == '\n' || win[i - 1] == '\r')) {
+              hit = true;
+              break;
+            }
+          if (hit) {
+            cut[t] = base + i;
+            break;
+          }
         }
-      } catch (const std::exception &e) {
-        ck[t].err = e.what();
+      }
+      if (bad) {
+        close(fd);
+        throw Error("cannot read " + path, 1);
+      }
+      lap("cut");
+      static const bool fast_lf = !getenv("MC_PARSE_LINES");  // (MC_PARSE_LINES=1: parse_chunk only)
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
+      for (int t = 0; t < T; t++) {
+        try {
+          if (cut[t] < cut[t + 1]) {
+            read_at(wbuf + cut[t], cut[t], cut[t + 1]);
+            if (bad) throw Error("cannot read " + path, 1);
+            if (fast_lf && !memchr(buf + cut[t], '\r', cut[t + 1] - cut[t]))
+              parse_chunk_lf(buf, cut[t], cut[t + 1], t == 0, cut[t + 1] == n, path, ck[t]);
+            else
+              parse_chunk(buf, cut[t], cut[t + 1], t == 0, cut[t + 1] == n, path, ck[t]);
+          }
+        } catch (const std::exception &e) {
+          ck[t].err = e.what();
+        }
       }
     }
     close(fd);
     // the first failing record in file order reports (the reference stops there)
     for (int t = 0; t < T; t++)
       if (!ck[t].err.empty()) throw Error(ck[t].err, 1);
+    if (!fq_err.empty()) throw Error(fq_err, 1);
     lap("chunks");
     // stitch: prefix sums over chunks, then parallel copies
     std::vector<uint64_t> rec0(T + 1, ds.size()), byte0(T + 1, ds.bases()), word0(T + 1, ds.pk_off.back()),
@@ -628,6 +768,7 @@ void parse_fasta_files(const std::vector<std::string> &files, Dataset &ds, int t
     ds.seg.resize(2 * seg0[T]);
     ds.exc_pos.resize(exc0[T]);
     ds.exc_val.resize(exc0[T]);
+    if (keep_qual) ds.qual.resize(byte0[T], 0);  // (FASTA records, and any parsed before without qualities: 0)
     {
       PodArray<uint32_t> grown;
       grown.resize(nwords);
@@ -652,6 +793,7 @@ void parse_fasta_files(const std::vector<std::string> &files, Dataset &ds, int t
         ds.seg_off[id + 1] = sg;
       }
       if (!c.pk.empty()) memcpy(ds.packed.data() + word0[t], c.pk.data(), c.pk.size() * 4);
+      if (!c.qual.empty()) memcpy(ds.qual.data() + byte0[t], c.qual.data(), c.qual.size());
       std::copy(c.seg.begin(), c.seg.end(), ds.seg.begin() + 2 * seg0[t]);
       for (size_t q = 0; q < c.exc_pos.size(); q++) {
         ds.exc_pos[exc0[t] + q] = byte0[t] + c.exc_pos[q];
@@ -661,6 +803,7 @@ void parse_fasta_files(const std::vector<std::string> &files, Dataset &ds, int t
     lap("stitch");
     ds.file_count.push_back(nr - rec0[0]);
     ds.file_len_sum.push_back(lsum);
+    ds.file_fastq.push_back(fastq ? 1 : 0);
   }
 }
 

@@ -4,6 +4,12 @@
 // ChromosomeOneDigit::encodeNucleotides (src/nonltr/ChromosomeOneDigit.cpp:95-144),
 // done in one parallel pass per file with 256-entry tables instead of std::map lookups.
 //
+// A file whose first non-empty line starts with '@' is FASTQ (decided per file): strict four-line
+// records, "@header", one sequence line, a line starting with '+', one quality line of the
+// sequence line's length; lines end at "\n" or "\r\n".  The sequence line goes through exactly what
+// a FASTA record's bytes go through and the stored header is '>' plus the rest of the '@' line, so
+// a FASTQ file and its FASTA twin give the same Dataset but for `qual` and `file_fastq`.
+//
 // The output is what the device consumes (mc_load_packed): 2-bit codes, 16 bases per 32-bit
 // word, every record starting on a word; the bytes a record keeps outside {0..3} (the 'N'
 // that encodeNucleotides leaves outside segments) as a sorted exception list.
@@ -60,13 +66,22 @@ struct Dataset {
   std::vector<uint64_t> file_count;  // records per input file
   std::vector<uint64_t> file_len_sum;  // sum of base.size() per file (Runner::find_k)
   std::vector<uint8_t> bytes_view;     // unpack_codes(), filled on demand (mcl_view)
+  std::vector<uint8_t> file_fastq;     // per input file: 1 if it was FASTQ
+  // Phred values (quality byte - 33, 0..93), one per expanded byte at seq_off; kept only by a parse
+  // that asks for them (then bases() long, the records of FASTA files holding 0), else empty
+  std::vector<uint8_t> qual;
   size_t size() const { return headers.size(); }
   uint64_t bases() const { return seq_off.empty() ? 0 : seq_off.back(); }
 };
 
 // Parses the files in the given order (the caller sorts by basename, Runner.cpp:253-262).
 // Throws mc::Error where the reference throws or crashes.
-void parse_fasta_files(const std::vector<std::string> &files, Dataset &ds, int threads);
+// keep_qual: FASTQ qualities are kept in ds.qual (otherwise they are checked and skipped).  A FASTQ
+// error is an Error of code 1 naming the file and the 1-based record.
+void parse_fasta_files(const std::vector<std::string> &files, Dataset &ds, int threads, bool keep_qual);
+inline void parse_fasta_files(const std::vector<std::string> &files, Dataset &ds, int threads) {
+  parse_fasta_files(files, ds, threads, false);
+}
 
 // The one-digit bytes of every record, concatenated (what ChromosomeOneDigit::getBase holds):
 // unpacked from `packed` + the exceptions.  For tests and the byte-level ABI.

@@ -51,6 +51,13 @@ traceback and pile-up (+ finish) device times (mc_nw_pileup_profile), the same w
 column (MC_PILEUP_NAIVE=1; the tables are compared), the bytes each call returns to the host and
 the atomics issued per pair against la + lb.
 
+--quality also times mc_nw_qpileup_strands (the pile-up weighed by base quality behind meshclust-assign
+--quality) on those pairs with a seeded quality 0 .. 93 on every byte, beside mc_nw_pileup_strands.  The
+count table and the integers of the two calls are compared first, and the weights of channels 0..4
+with the qualities of the aligned bases.  Adds the two calls' forward, traceback and pile-up
+(+ finish) device times, the atomics per pair, and how many columns the lane and the wave run
+forms take.
+
 Under rocprofv3 set MC_ACCUM_PLAIN_LAUNCH=1, as scripts/prof_round.sh does: the clustering's
 cooperative launch otherwise faults the profiler's exit handler, after the
 profile is written.
@@ -280,6 +287,73 @@ def pileup_phase(eng, lens, centres, queries, best, a):
     return out
 
 
+def quality_phase(eng, seq_off, centres, queries, best, a):
+    """Times mc_nw_qpileup_strands (the pile-up weighed by base quality behind --quality) beside
+    mc_nw_pileup_strands on the same pairs: every assigned read and its centre, every second read on
+    the minus strand, seeded qualities 0 .. 93 on every byte -> the keys for the line."""
+    has = best != M.ASSIGN_NONE
+    qa, cb = queries[has], centres[best[has]]
+    am = (np.arange(len(qa)) % 2).astype(np.uint8)
+    targets = np.unique(cb)
+    qual = np.random.default_rng(93).integers(0, M.QUAL_MAX + 1, int(seq_off[-1])).astype(np.uint8)
+    eng.load_qualities(qual)
+    out = {"quality_pairs": int(len(qa)), "quality_targets": int(len(targets))}
+    res = {}
+    for name in ("count", "quality"):
+        wall, fwd, tb, pu = [], [], [], []
+        for r in range(a.warmup + a.rounds):
+            eng.nw_pileup_profile(reset=True)
+            t0 = time.perf_counter()
+            got = eng.nw_pileup_strands(qa, cb, am, targets) if name == "count" else eng.nw_qpileup_strands(qa, cb, am, targets)
+            w = time.perf_counter() - t0
+            pr = eng.nw_pileup_profile()
+            if r >= a.warmup:
+                wall.append(w)
+                fwd.append(pr[0])
+                tb.append(pr[1])
+                pu.append(pr[2])
+        res[name] = got
+        out[name + "_call_wall_ms"] = round(1e3 * float(np.median(wall)), 3)
+        out[name + "_call_wall_ms_all"] = [round(1e3 * x, 3) for x in wall]
+        out[name + "_forward_device_ms"] = round(float(np.median(fwd)), 3)
+        out[name + "_traceback_device_ms"] = round(float(np.median(tb)), 3)
+        out[name + "_pileup_finish_device_ms"] = round(float(np.median(pu)), 3)
+        out[name + "_pileup_finish_device_ms_all"] = [round(x, 3) for x in pu]
+    tab, wtab, row_off, sc, ln, ids = res["quality"]
+    assert all(np.array_equal(x, y) for x, y in zip((tab, row_off, sc, ln, ids), res["count"])), "the count table or the integers differ"
+    assert not wtab[:, 7].any()
+    # with the words: what the weights must add up to, and the atomics the two run forms issue
+    words, off, _, _, _ = eng.nw_align_strands(qa, cb, am)
+    run, op = (words >> 4).astype(np.int64), words & 15
+    pair = np.repeat(np.arange(len(qa)), np.diff(off).astype(np.int64))
+    step = np.where(op != M.CIGAR_D, run, 0)
+    csum = np.cumsum(step) - step
+    start = csum - np.repeat(csum[off[:-1].astype(np.int64)], np.diff(off).astype(np.int64))  # the read bases before a run, in its pair
+    ins_q = 0  # the qualities of the inserted bases: they are in no column
+    for k in np.nonzero(op == M.CIGAR_I)[0]:
+        p, i0, n = int(pair[k]), int(start[k]), int(run[k])
+        q = qual[int(seq_off[qa[p]]):int(seq_off[qa[p] + 1])]
+        ins_q += int((q[::-1] if am[p] else q)[i0:i0 + n].astype(np.int64).sum())
+    read_q = sum(int(qual[int(seq_off[i]):int(seq_off[i + 1])].astype(np.int64).sum()) for i in qa)
+    assert int(wtab[:, :5].astype(np.int64).sum()) == read_q - ins_q, "the weights of channels 0..4 are not the aligned bases' qualities"
+    col = (op == M.CIGAR_EQ) | (op == M.CIGAR_X) | (op == M.CIGAR_D)
+    long_run = run > 8
+    m = len(qa)
+    out["quality_outputs_equal"] = True
+    out["quality_weight_atomics_per_pair"] = round((int(run[col].sum()) + int((op == M.CIGAR_I).sum())) / m, 2)
+    out["quality_count_atomics_per_pair"] = round((2 * int((op != M.CIGAR_X).sum()) + int(run[op == M.CIGAR_X].sum())) / m, 2)
+    out["quality_columns_by_wave_per_pair"] = round(int(run[col & long_run].sum()) / m, 2)
+    out["quality_columns_by_lane_per_pair"] = round(int(run[col & ~long_run].sum()) / m, 2)
+    out["quality_long_runs_per_pair"] = round(int((col & long_run).sum()) / m, 2)
+    out["quality_runs_per_pair"] = round(len(words) / m, 2)
+    out["quality_bytes_to_host"] = int(tab.nbytes + wtab.nbytes + row_off.nbytes + 12 * m)
+    out["quality_pileup_over_count_pileup"] = round(out["quality_pileup_finish_device_ms"] / out["count_pileup_finish_device_ms"], 3)
+    out["quality_pileup_share_of_kernels"] = round(out["quality_pileup_finish_device_ms"] / (
+        out["quality_forward_device_ms"] + out["quality_traceback_device_ms"] + out["quality_pileup_finish_device_ms"]), 4)
+    out["quality_call_over_count_call"] = round(out["quality_call_wall_ms"] / out["count_call_wall_ms"], 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=sorted(bench.WORKLOADS), default="B")
@@ -306,6 +380,10 @@ def main():
                     help="also time mc_nw_pileup_strands (the pile-up behind --consensus) over every read and its centre beside "
                          "mc_nw_align_strands on the same pairs: forward, traceback and pile-up device time, bytes returned, "
                          "atomics per pair, and the same with an atomic per column")
+    ap.add_argument("--quality", action="store_true",
+                    help="also time mc_nw_qpileup_strands (the weighted pile-up behind --quality) beside mc_nw_pileup_strands on "
+                         "the same pairs with seeded qualities: pile-up, forward and traceback device time, atomics per pair, and "
+                         "the columns the lane and the wave run forms take")
     a = ap.parse_args()
     n, templates, seed = bench.WORKLOADS[a.workload]
     fasta = bench.ensure_fasta(n, 1000, templates, 0.03, seed)
@@ -468,6 +546,8 @@ def main():
         line.update(align_phase(eng, lens, centres, queries, best, a))
     if a.pileup:
         line.update(pileup_phase(eng, lens, centres, queries, best, a))
+    if a.quality:
+        line.update(quality_phase(eng, seq_off, centres, queries, best, a))
     print(json.dumps(line))
     eng.close()
 
