@@ -247,6 +247,47 @@ int mc_assign_strands(mc_ctx *ctx, const uint32_t *centre_ids, uint32_t C, const
                       uint8_t *strand /* 0 plus, 1 minus; 0 when unassigned */, uint32_t *n_similar, uint64_t *stats);
 
 /*
+ * Strand-blind histograms: clustering reads whatever strand they were sequenced from.
+ *
+ * THE CANONICAL ROW of a point is canon[i] = row[i] + row[rc(i)] - 1, with row its pseudocount-1
+ * forward histogram and rc the index map of mc_revcomp_rows (host/strand.hpp): the pseudocount-1
+ * histogram of the record's k-mers counted on both strands.  It equals bit for bit the forward
+ * histogram of the record r || N x 30 || rc(r) with its second segment mirrored.  Its magnitude
+ * is 2 * mag - 4^k, its sum of squares is recomputed, the length stays the record's.  A record
+ * and its reverse complement have equal canonical rows wherever every segment is at least k long
+ * (every record of the parser; the exception is mc_revcomp_rows').  The largest canonical bin can
+ * need 16 bits where the forward one fits 8 (A x 150 || T x 150 at k = 4: 148 forward, 295
+ * canonical), so the width is chosen from the canonical maximum.
+ *
+ * mc_kmer_max_strands / mc_kmer_build_strands are mc_kmer_max / mc_kmer_build with a strand set:
+ *   strands == MC_STRAND_PLUS   forwards to mc_kmer_max / mc_kmer_build: the same kernels, the
+ *                               same results
+ *   strands == 3 (both)         `largest` is the largest canonical bin; the build leaves the
+ *                               canonical rows, their magnitudes and sums of squares as the
+ *                               context's histograms (K1, then one out-of-place fold kernel), so
+ *                               mc_get_histograms, mc_set_order, the scans, mean shift, mc_assign*
+ *                               and mc_classify_pairs work on them unchanged; the forward rows are
+ *                               kept in a second buffer for mc_orient_pairs.
+ * The width contract is mc_kmer_build's: the caller passes a width that holds `largest`.  strands
+ * outside {1, 3} is MC_ERR_ARG; with both strands 32/64-bit histograms and k >= 8 are
+ * MC_ERR_UNSUPPORTED.  A later mc_kmer_max / mc_kmer_build returns the context to forward rows and
+ * drops the second buffer.
+ *
+ * THE ORIENTATION OF A PAIR (a, b) is decided on the forward rows:
+ *   sad_plus = sum |row_a[i] - row_b[i]|,  sad_minus = sum |row_a[i] - row_b[rc(i)]|
+ * (exact integers); the strand is minus iff sad_minus < sad_plus, a tie is plus.
+ * mc_orient_pairs writes strand[p] (0 plus, 1 minus) and, sad given, sad[2p] = sad_plus and
+ * sad[2p + 1] = sad_minus for the m pairs.  Callers pass pairs grouped by b (many reads per
+ * centre): a workgroup stages row_b and its permuted row once per run of equal b; the results do
+ * not depend on the grouping.  MC_ERR_STATE unless the histograms were built with strands == 3;
+ * an id >= n (or m >= 2^32) is MC_ERR_ARG; m = 0 is MC_OK.
+ */
+int mc_kmer_max_strands(mc_ctx *ctx, int k, int strands /* 1 or 3 */, uint64_t *largest);
+int mc_kmer_build_strands(mc_ctx *ctx, int k, int width_bytes, int strands /* 1 or 3 */);
+int mc_orient_pairs(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, uint64_t m, uint8_t *strand /* m */,
+                    uint64_t *sad /* 2m, may be NULL */);
+
+/*
  * mc_assign_strands reporting the K best centres of every query instead of one.
  * A HIT of query q is a (centre index j, strand s) whose pair passes the length gate and is
  * classified similar: exactly the event that n_similar counts in mc_assign_strands.  With both

@@ -100,7 +100,8 @@ def gpu_lib():
                      "mc_scan_part", "mc_scan_commit", "mc_comm_unique_id", "mc_comm_create", "mc_comm_allgather",
                      "mc_comm_stats", "mc_comm_destroy", "mc_sync", "mc_assign", "mc_assign_strands",
                      "mc_revcomp_rows", "mc_assign_top", "mc_revcomp_sequences", "mc_nw_identity_strands",
-                     "mc_nw_align_strands", "mc_nw_align_profile", "mc_nw_pileup_strands", "mc_nw_pileup_profile"):
+                     "mc_nw_align_strands", "mc_nw_align_profile", "mc_nw_pileup_strands", "mc_nw_pileup_profile",
+                     "mc_kmer_max_strands", "mc_kmer_build_strands", "mc_orient_pairs"):
             getattr(lib, name).restype = C.c_int
         lib.mc_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
         lib.mc_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -122,6 +123,9 @@ def gpu_lib():
         lib.mc_nw_pileup_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mc_nw_pileup_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.mc_kmer_max_strands.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        lib.mc_kmer_build_strands.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        lib.mc_orient_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.mc_load_qualities.restype = C.c_int
         lib.mc_load_qualities.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         lib.mc_nw_qpileup_strands.restype = C.c_int
@@ -308,6 +312,31 @@ class Engine:
     def kmer_build(self, k, width):
         self._ck(self.lib.mc_kmer_build(self.ctx, k, width), "mc_kmer_build")
         self.width, self.B = width, 4 ** k
+
+    def kmer_max_strands(self, k, strands=MC_STRAND_PLUS | MC_STRAND_MINUS):
+        """mc_kmer_max_strands: the largest bin of the forward rows (strands 1) or of the canonical
+        rows row[i] + row[rc(i)] - 1 (strands 3)."""
+        out = C.c_uint64()
+        self._ck(self.lib.mc_kmer_max_strands(self.ctx, k, strands, C.byref(out)), "mc_kmer_max_strands")
+        return out.value
+
+    def kmer_build_strands(self, k, width, strands=MC_STRAND_PLUS | MC_STRAND_MINUS):
+        """mc_kmer_build_strands: strands 1 is kmer_build; strands 3 leaves the canonical rows as the
+        engine's histograms and keeps the forward rows for orient_pairs."""
+        self._ck(self.lib.mc_kmer_build_strands(self.ctx, k, width, strands), "mc_kmer_build_strands")
+        self.width, self.B = width, 4 ** k
+
+    def orient_pairs(self, a, b, sad=True):
+        """mc_orient_pairs on the forward rows: strand[p] = 1 iff sum |row_a - row_b[rc]| <
+        sum |row_a - row_b| -> (strand, sad[m, 2] = (plus, minus) or None).  Pass pairs grouped by b."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        assert len(a) == len(b)
+        strand = np.zeros(len(a), np.uint8)
+        sums = np.zeros((len(a), 2), np.uint64) if sad else None
+        self._ck(self.lib.mc_orient_pairs(self.ctx, _p(a), _p(b), C.c_uint64(len(a)), _p(strand),
+                                          _p(sums) if sad else None), "mc_orient_pairs")
+        return strand, sums
 
     def histograms(self):
         dt = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[self.width]
@@ -790,6 +819,24 @@ class Dataset:
                         [[int(s[j]), int(s[j + 1])] for j in range(0, len(s), 2)]))
         return out
 
+    def label_identities(self, engine, a, b, both_strands=False):
+        """mcl_label_identities: the identities the trainer labels the pairs (a[i], b[i]) with (its
+        only alignment seam); ``both_strands``: max(identity(a, b), identity(rc(a), b)), what a
+        ``--both-strands`` run trains on.  The dataset's sequences must be loaded in ``engine``."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        assert len(a) == len(b)
+        out = np.zeros(len(a))
+        err = C.create_string_buffer(1024)
+        self.lib.mcl_label_identities.restype = C.c_int
+        self.lib.mcl_label_identities.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
+                                                  C.c_void_p, C.c_char_p, C.c_int]
+        rc = self.lib.mcl_label_identities(self.h, engine.ctx, _p(a), _p(b), len(a), 1 if both_strands else 0, _p(out),
+                                           err, 1024)
+        if rc != 0:
+            raise MCError("mcl_label_identities failed (%d): %s" % (rc, err.value.decode()))
+        return out
+
     def run(self, engine, args=(), upload=True, clstr=None, comm=None):
         """Run the full pipeline (reference options in ``args``); returns the stats dict.
         ``comm`` (meshclust_amd.dist.RcclShardComm or TorchShardComm) shares the clustering
@@ -808,6 +855,9 @@ class Dataset:
         st = json.loads(buf.value.decode() or "{}")
         if rc != 0 or "error" in st:  # incl. the reference's exit(0) stops (no partition)
             raise MCError("mcl_run failed (%d): %s" % (rc, st))
+        if upload:  # the engine now holds this dataset's sequences (histograms() sizes its arrays by n)
+            engine.n = self.n
+        engine.width, engine.B = st.get("width", engine.width), 4 ** st["k"] if "k" in st else engine.B
         return st
 
     def __del__(self):

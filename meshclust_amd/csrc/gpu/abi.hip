@@ -300,7 +300,7 @@ int mc_ctx_destroy(mc_ctx *c) {
                  &c->s_c, &c->s_d, &c->s_e, &c->s_f, &c->s_g, &c->s_h, &c->s_i, &c->s_j, &c->s_k, &c->hs, &c->mag_s, &c->sumsq_s, &c->len_s, &c->ticket,
                  &c->msum, &c->ident_s, &c->al_a, &c->al_b, &c->al_out, &c->al_id, &c->ord_ids, &c->acc_out, &c->sp_words, &c->sp_keys,
                  &c->sp_scr, &c->sp_nodes, &c->sp_nn, &c->sp_q, &c->sp_err, &c->u_off, &c->u_mem, &c->nw_items, &c->nw_gran, &c->rc_seq, &c->tr_choice, &c->tr_bnd, &c->tr_ops, &c->tr_pairs, &c->tr_res, &c->tr_idx, &c->tr_dst,
-                 &c->tr_out, &c->tr_err, &c->pu_table, &c->pu_diff, &c->pu_rows, &c->pu_toff, &c->pu_roff, &c->qual, &c->pu_wtable, &c->pu_qoff})
+                 &c->tr_out, &c->tr_err, &c->pu_table, &c->pu_diff, &c->pu_rows, &c->pu_toff, &c->pu_roff, &c->qual, &c->pu_wtable, &c->pu_qoff, &c->hist_fwd, &c->or_runs})
     release(*b);
   if (c->h_scan) (void)hipHostFree(c->h_scan);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -326,6 +326,8 @@ static int load_common(mc_ctx *c, const uint64_t *seq_off, uint64_t n, const int
   c->n = n;
   c->k = 0;
   c->kmer_spec_k = 0;
+  c->canon = false;
+  release(c->hist_fwd);
   c->h_seq_off.assign(seq_off, seq_off + n + 1);
   if (pk_off.empty()) {
     pk_off.resize(n + 1);
@@ -415,6 +417,8 @@ static int kmer_common(mc_ctx *c, int k, int width, bool write, uint64_t *larges
   int *d_err = (int *)((char *)c->s_f.p + 8);
   c->k = 0;  // rows are being (re)written
   c->kmer_spec_k = 0;
+  c->canon = false;  // ... as forward rows: the canonical rows' second buffer goes
+  release(c->hist_fwd);
   c->B = 1 << (2 * k);
   c->width = width;
   c->pitch = ((uint64_t)c->B * width + 15) / 16 * 16;
@@ -453,6 +457,99 @@ int mc_kmer_build(mc_ctx *c, int k, int width) {
   if (c->kmer_spec_k == k && width == 1 && c->k == k) return MC_OK;  // written by mc_kmer_max
   TRY(kmer_common(c, k, width, true, nullptr));
   c->k = k;
+  return MC_OK;
+}
+
+// ---- strand-blind histograms (canon.hip) ----------------------------------------------------
+static int strands_check(mc_ctx *c, const char *who, int k, int strands) {
+  if (!c || (strands != MC_STRAND_PLUS && strands != (MC_STRAND_PLUS | MC_STRAND_MINUS))) {
+    set_error(std::string(who) + ": strands must be MC_STRAND_PLUS or MC_STRAND_PLUS | MC_STRAND_MINUS");
+    return MC_ERR_ARG;
+  }
+  if (strands != MC_STRAND_PLUS && k >= 8) {
+    set_error(std::string(who) + ": a histogram row does not fit an LDS tile (k >= 8)");
+    return MC_ERR_UNSUPPORTED;
+  }
+  return MC_OK;
+}
+
+// the largest canonical bin of the forward rows in c->hist (c->k, c->width valid)
+static int canon_max(mc_ctx *c, uint64_t *largest) {
+  TRY(ensure(c->s_f, 64));
+  MCG_CHECK(hipMemsetAsync(c->s_f.p, 0, 64, c->stream));
+  TRY(launch_canon_rows(c, (const uint8_t *)c->hist.p, nullptr, (uint64_t *)c->s_f.p));
+  uint64_t h = 0;
+  MCG_CHECK(hipMemcpyAsync(&h, c->s_f.p, 8, hipMemcpyDeviceToHost, c->stream));
+  MCG_CHECK(hipStreamSynchronize(c->stream));
+  flush_timers(c);
+  *largest = h;
+  return MC_OK;
+}
+
+int mc_kmer_max_strands(mc_ctx *c, int k, int strands, uint64_t *largest) {
+  TRY(strands_check(c, "mc_kmer_max_strands", k, strands));
+  if (strands == MC_STRAND_PLUS) return mc_kmer_max(c, k, largest);
+  uint64_t mx = 0;
+  TRY(mc_kmer_max(c, k, &mx));  // forward rows at 8 bits where they fit (K1 runs once)
+  if (mx > 0xff) {               // they do not: forward rows at 16 bits for the fold to read
+    if (mx > 0xffff) {
+      set_error("mc_kmer_max_strands: 32/64-bit histograms are not supported");
+      return MC_ERR_UNSUPPORTED;
+    }
+    TRY(kmer_common(c, k, 2, true, nullptr));
+    c->k = k;
+  }
+  TRY(canon_max(c, &mx));
+  if (largest) *largest = mx;
+  return MC_OK;
+}
+
+int mc_kmer_build_strands(mc_ctx *c, int k, int width, int strands) {
+  TRY(strands_check(c, "mc_kmer_build_strands", k, strands));
+  if (strands == MC_STRAND_PLUS) return mc_kmer_build(c, k, width);
+  if (width != 1 && width != 2 && width != 4 && width != 8) return MC_ERR_ARG;
+  if (width != 1 && width != 2) {
+    set_error("mc_kmer_build_strands: 32/64-bit histograms are not supported");
+    return MC_ERR_UNSUPPORTED;
+  }
+  // forward rows at the canonical width (canon[i] >= row[i]: what holds the one holds the other);
+  // mc_kmer_max_strands left them where the width is the one it read them at
+  if (!(c->k == k && c->width == width && !c->canon && c->n > 0)) TRY(mc_kmer_build(c, k, width));
+  TRY(ensure(c->hist_fwd, c->n * c->pitch));
+  TRY(ensure(c->s_f, 64));
+  MCG_CHECK(hipMemsetAsync(c->s_f.p, 0, 64, c->stream));
+  TRY(launch_canon_rows(c, (const uint8_t *)c->hist.p, (uint8_t *)c->hist_fwd.p, (uint64_t *)c->s_f.p));
+  MCG_CHECK(hipStreamSynchronize(c->stream));
+  flush_timers(c);
+  std::swap(c->hist, c->hist_fwd);  // hist: the canonical rows; hist_fwd: K1's
+  c->canon = true;
+  c->kmer_spec_k = 0;  // (a plain mc_kmer_build of this k must run K1 again)
+  return MC_OK;
+}
+
+int mc_orient_pairs(mc_ctx *c, const uint32_t *a, const uint32_t *b, uint64_t m, uint8_t *strand, uint64_t *sad) {
+  if (!c || c->k == 0 || !c->canon) {
+    set_error("mc_orient_pairs: the histograms were not built with mc_kmer_build_strands(strands == 3)");
+    return MC_ERR_STATE;
+  }
+  if (m == 0) return MC_OK;
+  if (!a || !b || !strand || m >= (1ull << 32)) {
+    set_error("mc_orient_pairs: no pairs (or no output)");
+    return MC_ERR_ARG;
+  }
+  for (uint64_t i = 0; i < m; i++)
+    if (a[i] >= c->n || b[i] >= c->n) {
+      set_error("point id out of range");
+      return MC_ERR_ARG;
+    }
+  MCG_CHECK(hipSetDevice(c->device));
+  TRY(upload(c, c->s_a, a, m, c->stream));
+  TRY(ensure(c->s_b, m + 16));
+  if (sad) TRY(ensure(c->s_c, 2 * m * 8 + 16));
+  TRY(launch_orient(c, (const uint8_t *)c->hist_fwd.p, (const uint32_t *)c->s_a.p, b, m, c->or_runs, (uint8_t *)c->s_b.p,
+                    sad ? (uint64_t *)c->s_c.p : nullptr));
+  TRY(download_parts(c, {{strand, c->s_b.p, (size_t)m}, {sad, c->s_c.p, sad ? (size_t)m * 16 : 0}}, c->stream));
+  flush_timers(c);
   return MC_OK;
 }
 

@@ -130,6 +130,11 @@ struct mc_ctx {
   int k = 0, B = 0, width = 0;
   uint64_t pitch = 0;
   mcg::Buf hist, mag, sumsq, len;
+  // mc_kmer_build_strands(strands == 3): hist / mag / sumsq hold the canonical rows (canon.hip) and
+  // hist_fwd keeps K1's forward rows at the same width and pitch for mc_orient_pairs; any later
+  // K1 pass returns the context to forward rows and frees hist_fwd
+  bool canon = false;
+  mcg::Buf hist_fwd, or_runs;
   // classifier
   mcg::DevClassifier cls{};
   mcg::FastCls fcls{};
@@ -272,6 +277,14 @@ int launch_nw(mc_ctx *c, const uint8_t *d_A, const uint64_t *d_aoff, const uint3
 // 16-byte-padded offsets d_out_off[u + 1] (out_bytes = its last entry); timed as F_LAYOUT
 int launch_revseq(mc_ctx *c, const uint32_t *d_ids, uint32_t u, const uint64_t *d_out_off, uint64_t out_bytes,
                   uint8_t *d_out);
+
+// canon.hip: the fold over the n forward rows d_in (the context's k, width, pitch) -- canonical
+// rows to d_out with their mag / sumsq to the context's (d_out null: neither), the largest
+// canonical bin max-ed into *d_max; the strands (d_sad given: and both sums) of the m pairs
+// (d_a[p], h_b[p]) on the forward rows d_fwd, h_b cut into runs of equal b (uploaded to `runs`)
+int launch_canon_rows(mc_ctx *c, const uint8_t *d_in, uint8_t *d_out, uint64_t *d_max);
+int launch_orient(mc_ctx *c, const uint8_t *d_fwd, const uint32_t *d_a, const uint32_t *h_b, uint64_t m, Buf &runs,
+                  uint8_t *d_strand, uint64_t *d_sad);
 
 // nwtrace.hip: rows per lane and choice bytes of a pair; the forward and traceback kernels over
 // a batch (results to d_res, TRACE_RES ints per pair; operation words to each pair's region of

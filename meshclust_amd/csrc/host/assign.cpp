@@ -28,6 +28,10 @@ static const char *kUsage =
     "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--consensus FILE] "
     "[--pileup FILE] [--quality] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
+    "                  (implied by a version-2 model, saved by meshclust --both-strands: reads and centres are then\n"
+    "                  scored once on their canonical rows and every hit's strand comes from mc_orient_pairs; with\n"
+    "                  such a model MC_ASSIGN_PAIRS scores the pair list on the canonical rows too, and 32/64-bit\n"
+    "                  histograms or k >= 8 are refused with exit code 2)\n"
     "  --top K --hits FILE  (given together, K = 1..8) also write the K best similar centres of every read to\n"
     "                  FILE: read, rank, centre, cluster index, combo 0 (and the strand with --both-strands)\n"
     "  --identity      align every reported (read, centre) pair, the read reverse-complemented where it was\n"
@@ -310,7 +314,8 @@ static void pileup_outputs(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std
   if (!opt.pileup.empty()) write_text(opt.pileup, tsv);
 }
 
-AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
+AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
+  AssignOptions opt = opt_in;
   AssignResult r;
   struct Own {  // a context of the tool's own, opened only once the inputs are accepted
     mc_ctx *c = nullptr;
@@ -327,8 +332,20 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   bool by_pairs = getenv("MC_ASSIGN_PAIRS") && atoi(getenv("MC_ASSIGN_PAIRS")) != 0;
   // the pair list has no permuted rows: never score one strand where two were asked for
   const char *no_strands = "meshclust-assign: --both-strands needs the device kernel (mc_assign_strands), which does not apply here: ";
-  if (by_pairs && opt.both_strands) throw Error(std::string(no_strands) + "MC_ASSIGN_PAIRS is set", 2);
+  if (by_pairs && opt.both_strands) {  // (refused before anything else is read; a version-2 model has its own rows)
+    bool v2 = false;
+    try {
+      v2 = read_model(opt.model).strands != 1;
+    } catch (const Error &) {
+    }
+    if (!v2) throw Error(std::string(no_strands) + "MC_ASSIGN_PAIRS is set", 2);
+  }
   const Model model = read_model(opt.model);
+  // a version-2 model (meshclust --both-strands): reads and centres as canonical rows, scored once
+  // (the rows are symmetric: a minus pass would list every hit twice), every reported hit's strand
+  // from mc_orient_pairs on the forward rows; from there on the job runs as with --both-strands
+  const bool canon = model.strands != 1;
+  if (canon) opt.both_strands = true;
   if (model.align)
     throw Error("meshclust-assign: " + opt.model +
                     " is an alignment-mode model (--align or --id below 0.6); only k-mer classifiers can be assigned against",
@@ -367,11 +384,24 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   r.upload_ms = ms_since(t0);
   t0 = std::chrono::steady_clock::now();
   uint64_t largest = 0;
-  check(mc_kmer_max(ctx, model.k, &largest), "mc_kmer_max");
+  const char *no_canon = "meshclust-assign: a version-2 model (meshclust --both-strands) needs canonical rows, which this input cannot have: ";
+  if (canon) {
+    const int rc = mc_kmer_max_strands(ctx, model.k, model.strands, &largest);
+    if (rc == MC_ERR_UNSUPPORTED) throw Error(std::string(no_canon) + mc_last_error(), 2);
+    check(rc, "mc_kmer_max_strands");
+  } else {
+    check(mc_kmer_max(ctx, model.k, &largest), "mc_kmer_max");
+  }
   int width = largest <= 0xff ? 1 : largest <= 0xffff ? 2 : largest <= 0xffffffffull ? 4 : 8;  // as run_pipeline
   if (const char *fw = getenv("MC_FORCE_WIDTH")) width = std::max(width, atoi(fw));
   r.width = width;
-  check(mc_kmer_build(ctx, model.k, width), "mc_kmer_build");
+  if (canon) {
+    const int rc = mc_kmer_build_strands(ctx, model.k, width, model.strands);
+    if (rc == MC_ERR_UNSUPPORTED) throw Error(std::string(no_canon) + mc_last_error(), 2);
+    check(rc, "mc_kmer_build_strands");
+  } else {
+    check(mc_kmer_build(ctx, model.k, width), "mc_kmer_build");
+  }
   check(mc_set_classifier(ctx, &model.cls), "mc_set_classifier");
   r.kmer_ms = ms_since(t0);
   t0 = std::chrono::steady_clock::now();
@@ -393,15 +423,16 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
     for (uint64_t j = 0; j < C; j++) cid[j] = (uint32_t)j;
     for (uint64_t q = 0; q < M; q++) qid[q] = (uint32_t)(C + q);
     uint64_t st[3] = {0, 0, 0};
+    const int score = canon ? MC_STRAND_PLUS : r.strands;  // canonical rows: the plus strand set only
     const int rc = K > 0
-                       ? mc_assign_top(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, r.strands, K, hit.data(),
+                       ? mc_assign_top(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, score, K, hit.data(),
                                        hit_val.data(), hit_strand.data(), nsim.data(), st)
-                   : opt.both_strands
-                       ? mc_assign_strands(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, r.strands, best.data(),
+                   : opt.both_strands && !canon
+                       ? mc_assign_strands(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, score, best.data(),
                                            val.data(), strand.data(), nsim.data(), st)
                        : mc_assign(ctx, cid.data(), (uint32_t)C, qid.data(), M, model.id, best.data(), val.data(),
                                    nsim.data(), st);
-    if (rc == MC_ERR_UNSUPPORTED && opt.both_strands) throw Error(std::string(no_strands) + mc_last_error(), 2);
+    if (rc == MC_ERR_UNSUPPORTED && opt.both_strands && !canon) throw Error(std::string(no_strands) + mc_last_error(), 2);
     if (rc == MC_ERR_UNSUPPORTED) {  // wide bins or rows: the pair list does the same job
       if (!opt.quiet) fprintf(stderr, "meshclust-assign: %s; scoring with mc_classify_pairs\n", mc_last_error());
       by_pairs = true;
@@ -420,6 +451,26 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt) {
   }
   if (by_pairs) {
     assign_by_pairs(ctx, ds, (uint32_t)C, M, model.id, best, val, nsim, &r.candidates, K, hit, hit_val);
+  }
+  if (canon) {
+    // the strand of every reported (read, centre): mc_orient_pairs, the pairs grouped by centre
+    const uint32_t Kr = K > 0 ? K : 1;
+    const uint32_t *cj = K > 0 ? hit.data() : best.data();
+    std::vector<uint64_t> slot;
+    for (uint64_t q = 0; q < M; q++)
+      for (uint32_t t = 0; t < Kr && cj[q * Kr + t] != MC_ASSIGN_NONE; t++) slot.push_back(q * Kr + t);
+    std::stable_sort(slot.begin(), slot.end(), [&](uint64_t x, uint64_t y) { return cj[x] < cj[y]; });
+    std::vector<uint32_t> oa(slot.size()), ob(slot.size());
+    for (size_t p = 0; p < slot.size(); p++) {
+      oa[p] = (uint32_t)(C + slot[p] / Kr);
+      ob[p] = cj[slot[p]];
+    }
+    std::vector<uint8_t> os(slot.size(), 0);
+    check(mc_orient_pairs(ctx, oa.data(), ob.data(), slot.size(), os.data(), nullptr), "mc_orient_pairs");
+    for (size_t p = 0; p < slot.size(); p++) {
+      if (K > 0) hit_strand[slot[p]] = os[p];
+      if (slot[p] % Kr == 0) strand[slot[p] / Kr] = os[p];
+    }
   }
   r.path = by_pairs ? "pairs" : "device";
   r.assign_ms = ms_since(t0);

@@ -54,6 +54,13 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // column (+, -, or * for an unassigned read); where only the pair list applies (MC_ASSIGN_PAIRS,
 // wide bins or rows) both_strands throws an Error of code 2: the pair list has no permuted rows.  ctx NULL: a context on opt.device is
 // opened once the model and the centres file are accepted, and closed at the end.
+// A version-2 model (meshclust --both-strands, model.hpp: strands 3) implies both_strands: reads and
+// centres get canonical rows (mc_kmer_max_strands / mc_kmer_build_strands), the plus strand set
+// alone is scored (the rows are symmetric: a minus pass would list every hit twice), and the strand
+// of every reported (read, centre) comes from mc_orient_pairs; everything after that runs as with
+// both_strands.  There the pair list (MC_ASSIGN_PAIRS, rows too wide for the kernel) runs on the
+// canonical rows too; an input that cannot have canonical rows (32/64-bit bins, k >= 8) throws an
+// Error of code 2.  A version-1 model behaves as before.
 // With top / hits (mc_assign_top; on the pair list the same ordered insertion on the host) the
 // hits file gets one line per hit (read, rank, centre, cluster index, combo 0, and the strand
 // with both_strands); the TSV is the one written without them.

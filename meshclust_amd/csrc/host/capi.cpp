@@ -103,6 +103,7 @@ static int run_common(void *dsv, mc_ctx *ctx, int argc, char **argv, int upload,
     const auto t1 = std::chrono::steady_clock::now();
     if (clstr_path) mc::write_clstr(clstr_path, *ds, rr.part, opt.threads > 0 ? opt.threads : 1);
     if (!comm || comm->rank == 0) mc::save_model_files(opt, *ds, rr);
+    if (!opt.strands_file.empty() && (!comm || comm->rank == 0)) mc::write_strands_file(opt.strands_file, *ds, rr);
     const double write_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     std::string js = mc::stats_json(rr, 0, write_ms);
     if (stats && cap > 0) snprintf(stats, cap, "%s", js.c_str());
@@ -112,6 +113,35 @@ static int run_common(void *dsv, mc_ctx *ctx, int argc, char **argv, int upload,
     return e.code;
   } catch (const std::exception &e) {
     put_error(stats, cap, e.what(), 1);
+    return 1;
+  }
+}
+
+// The identities Trainer::nw_batch labels the m pairs (a[i], b[i]) with: mc_nw_identity's, or with
+// both_strands != 0 max(identity(a, b), identity(rc(a), b)) -- what a --both-strands run trains on.
+// The sequences of `dsv` must be loaded in ctx.  Returns 0 or an exit code with the message in err.
+int mcl_label_identities(void *dsv, mc_ctx *ctx, const uint32_t *a, const uint32_t *b, uint64_t m, int both_strands,
+                         double *ident, char *err, int errcap) {
+  auto *ds = (mc::Dataset *)dsv;
+  try {
+    mc::TrainerConfig tc;
+    tc.both_strands = both_strands != 0;
+    mc::PhaseTimer timer;
+    mc::Trainer tr(*ds, ctx, tc, timer);
+    std::vector<mc::PairId> pairs(m);
+    for (uint64_t i = 0; i < m; i++) {
+      if (a[i] >= ds->size() || b[i] >= ds->size()) throw mc::Error("pair id out of range", 1);
+      pairs[i] = mc::PairId(a[i], b[i]);
+    }
+    std::vector<double> id;
+    tr.nw_batch(pairs, id);
+    for (uint64_t i = 0; i < m; i++) ident[i] = id[i];
+    return 0;
+  } catch (const mc::Error &e) {
+    if (err && errcap > 0) snprintf(err, errcap, "%s", e.what());
+    return e.code ? e.code : 1;
+  } catch (const std::exception &e) {
+    if (err && errcap > 0) snprintf(err, errcap, "%s", e.what());
     return 1;
   }
 }

@@ -11,6 +11,17 @@
 
 #include "../../../include/meshclust_amd.h"
 
+// The strand-blind entries (meshclust --both-strands) as weak references: bin/meshclust's objects
+// are also linked against the CPU oracle engine of the test harness, which has none of them.
+// A null address is reported as an error that names the engine (strands_engine_check).
+extern "C" {
+int mc_kmer_max_strands(mc_ctx *, int, int, uint64_t *) __attribute__((weak));
+int mc_kmer_build_strands(mc_ctx *, int, int, int) __attribute__((weak));
+int mc_orient_pairs(mc_ctx *, const uint32_t *, const uint32_t *, uint64_t, uint8_t *, uint64_t *) __attribute__((weak));
+int mc_nw_identity_strands(mc_ctx *, const uint32_t *, const uint32_t *, const uint8_t *, uint64_t, double *, int32_t *,
+                           int32_t *) __attribute__((weak));
+}
+
 namespace mc {
 
 // Error the reference would raise (uncaught exception / exit).  The driver prints it and
@@ -45,6 +56,15 @@ inline void check(int rc, const char *what) {
     const char *e = mc_last_error();
     throw Error(std::string(what) + " failed: " + (e ? e : "?"), 3);
   }
+}
+
+// --both-strands needs the four entries above; the CPU oracle engine lacks them.
+inline void strands_engine_check() {
+  if (!mc_kmer_max_strands || !mc_kmer_build_strands || !mc_orient_pairs || !mc_nw_identity_strands)
+    throw Error("--both-strands: the engine this program is linked against has no strand-blind histograms "
+                "(mc_kmer_max_strands, mc_kmer_build_strands, mc_orient_pairs, mc_nw_identity_strands); "
+                "they exist in the GPU engine libmcgpu only",
+                1);
 }
 
 // Per-phase wall-clock accounting (printed with --timing, read by bench.py).

@@ -1,7 +1,9 @@
 // model.hpp -- what read assignment needs from a finished clustering, as two files:
 //   the model   a text file, first line "meshclust-model 1", then `key value...` lines: k, id,
 //               align, every field of mc_classifier, the number of centres.  Doubles are C99 hex
-//               floats (%a), so a reload is bit-exact.
+//               floats (%a), so a reload is bit-exact.  A clustering on both strands (meshclust
+//               --both-strands: canonical rows) writes "meshclust-model 2" and a line "strands 3"
+//               after align; version 1 means strands 1, a version 2 without `strands` is refused.
 //   the centres a FASTA of the final centres in cluster order: header lines unchanged, each
 //               sequence on one line, ACGT for the codes 0..3 and the stored exception byte
 //               elsewhere -- re-parsing gives the same lengths, segments and in-segment codes.
@@ -27,13 +29,14 @@ struct Model {
   int k = 0;
   double id = 0;
   int align = 0;
+  int strands = 1;  // 3: trained and clustered on canonical rows (version 2)
   mc_classifier cls;
   uint64_t centres = 0;
   Model() { memset(&cls, 0, sizeof cls); }
 };
 
 inline std::string model_text(const Model &m) {
-  std::string o = "meshclust-model 1\n";
+  std::string o = m.strands == 1 ? "meshclust-model 1\n" : "meshclust-model 2\n";
   char b[64];
   auto ints = [&](const char *key, const long long *v, int n) {
     o += key;
@@ -57,6 +60,7 @@ inline std::string model_text(const Model &m) {
   one("k", m.k);
   dbls("id", &m.id, 1);
   one("align", m.align);
+  if (m.strands != 1) one("strands", m.strands);
   one("n_single", c.n_single);
   for (int i = 0; i < MC_MAX_SINGLE; i++) t[i] = c.lookup[i];
   ints("lookup", t, MC_MAX_SINGLE);
@@ -90,8 +94,9 @@ inline void write_model(const std::string &path, const Model &m) {
 inline Model parse_model(const std::string &text, const std::string &name) {
   std::istringstream in(text);
   std::string line;
-  if (!std::getline(in, line) || line != "meshclust-model 1")
-    throw Error(name + ": not a meshclust model (first line must be \"meshclust-model 1\")");
+  if (!std::getline(in, line) || (line != "meshclust-model 1" && line != "meshclust-model 2"))
+    throw Error(name + ": not a meshclust model (first line must be \"meshclust-model 1\" or \"meshclust-model 2\")");
+  const int version = line.back() - '0';
   std::map<std::string, std::vector<std::string>> kv;
   while (std::getline(in, line)) {
     std::istringstream ls(line);
@@ -126,6 +131,10 @@ inline Model parse_model(const std::string &text, const std::string &name) {
   m.k = (int)to_ll(get("k", 1)[0]);
   m.id = to_d(get("id", 1)[0]);
   m.align = (int)to_ll(get("align", 1)[0]);
+  if (version >= 2) {
+    m.strands = (int)to_ll(get("strands", 1)[0]);
+    if (m.strands != 1 && m.strands != 3) throw Error(name + ": strands must be 1 or 3");
+  }
   c.n_single = (int32_t)to_ll(get("n_single", 1)[0]);
   c.n_combo = (int32_t)to_ll(get("n_combo", 1)[0]);
   for (int i = 0; i < MC_MAX_SINGLE; i++) {

@@ -32,8 +32,11 @@ namespace mc {
 static void usage(const char *prog) {
   printf("Usage: %s *.fasta [--id 0.90] [--kmer 3] [--delta 5] [--output output.clstr] [--iterations 20] "
          "[--align] [--sample 3000] [--pivot 40] [--threads TMAX] [--device GPU] [--devices GPU,GPU,..] "
-         "[--stats-json FILE] [--save-model FILE] [--save-centres FILE]\n",
+         "[--stats-json FILE] [--save-model FILE] [--save-centres FILE] [--both-strands [--strands FILE]]\n",
          prog);
+  printf("  --both-strands  cluster reads whatever strand they were sequenced from (k-mers counted on both strands;\n"
+         "                  not with --align or --id below 0.6); --strands FILE: name, cluster, centre, +|-, sad_plus,\n"
+         "                  sad_minus per read in .clstr order\n");
   printf("MI355X-native MeShClust (meshclust_amd, C-ABI v%d)\n", MC_ABI_VERSION);
 }
 
@@ -104,6 +107,10 @@ Options parse_options(int argc, char **argv, bool require_files) {
       o.save_model = argv[++i];
     } else if (arg == "--save-centres" && i + 1 < argc) {
       o.save_centres = argv[++i];
+    } else if (arg == "--both-strands") {
+      o.both_strands = true;
+    } else if (arg == "--strands" && i + 1 < argc) {
+      o.strands_file = argv[++i];
     } else if (arg == "--quiet") {
       o.quiet = true;
     } else {
@@ -112,6 +119,14 @@ Options parse_options(int argc, char **argv, bool require_files) {
       else throw OptionError(std::string("unknown option or missing file: ") + argv[i], EXIT_FAILURE, true);
     }
   }
+  // never cluster on one strand in silence: alignment mode has no second strand
+  if (o.both_strands && o.align)
+    throw OptionError("--both-strands cannot be combined with --align (alignment mode runs on one strand)", EXIT_FAILURE, false);
+  if (o.both_strands && o.similarity < 0.6)
+    throw OptionError("--both-strands cannot be combined with --id below 0.6, which switches --align on "
+                      "(alignment mode runs on one strand)",
+                      EXIT_FAILURE, false);
+  if (!o.strands_file.empty() && !o.both_strands) throw OptionError("--strands needs --both-strands", EXIT_FAILURE, false);
   if (o.files.empty() && require_files) throw OptionError("no input files", EXIT_FAILURE, true);
   std::sort(o.files.begin(), o.files.end(), [](const std::string &a, const std::string &b) {
     char *as = strdup(a.c_str()), *bs = strdup(b.c_str());
@@ -124,12 +139,26 @@ Options parse_options(int argc, char **argv, bool require_files) {
 }
 
 // Runner::find_k (Runner.cpp:265-292): integer mean length per file, mean over files.
-static int find_k(const Dataset &ds, bool verbose) {
+int recommended_k(unsigned long long length) { return (int)std::ceil(std::log((double)length) / std::log(4)) - 1; }
+
+static unsigned long long mean_length(const Dataset &ds) {
   unsigned long long length = 0;
   for (size_t f = 0; f < ds.file_count.size(); f++) length += ds.file_len_sum[f] / ds.file_count[f];
-  length /= ds.file_count.size();
-  int newk = (int)std::ceil(std::log((double)length) / std::log(4)) - 1;
+  return length / ds.file_count.size();
+}
+
+static int find_k(const Dataset &ds, bool verbose) {
+  const unsigned long long length = mean_length(ds);
+  int newk = recommended_k(length);
   if (verbose) printf("avg length: %llu\nRecommended K: %d\n", length, newk);
+  return newk;
+}
+
+// --both-strands: the canonical row counts 2(L - k + 1) k-mers into about half as many independent
+// bins, so the same formula runs on twice the integer mean length
+static int find_k_strands(unsigned long long doubled, bool verbose) {
+  int newk = recommended_k(doubled);
+  if (verbose) printf("avg length: %llu (both strands: %llu)\nRecommended K: %d\n", doubled / 2, doubled, newk);
   return newk;
 }
 
@@ -236,6 +265,13 @@ RunResult run_pipeline(const Dataset &ds, mc_ctx *ctx, Options opt, bool upload,
 #else
   threads = 1;
 #endif
+  if (opt.both_strands) {
+    if (opt.align || opt.similarity < 0.6) throw Error("--both-strands cannot be combined with --align or --id below 0.6", 1);
+    strands_engine_check();
+    rr.strands = MC_STRAND_PLUS | MC_STRAND_MINUS;
+    rr.k_auto_length = 2 * mean_length(ds);
+    if (opt.k == -1) opt.k = find_k_strands(rr.k_auto_length, verbose);
+  }
   if (opt.k == -1) opt.k = find_k(ds, verbose);
   if (opt.similarity < 0.6) opt.align = true;
   if (opt.sample_size == 0) opt.sample_size = 3000;
@@ -300,14 +336,16 @@ RunResult run_pipeline(const Dataset &ds, mc_ctx *ctx, Options opt, bool upload,
   }
   {
     Scope s(rr.timer, "kmer");
-    check(mc_kmer_max(ctx, opt.k, &rr.largest), "mc_kmer_max");
+    if (opt.both_strands) check(mc_kmer_max_strands(ctx, opt.k, rr.strands, &rr.largest), "mc_kmer_max_strands");
+    else check(mc_kmer_max(ctx, opt.k, &rr.largest), "mc_kmer_max");
     int width = rr.largest <= 0xff ? 1 : rr.largest <= 0xffff ? 2 : rr.largest <= 0xffffffffull ? 4 : 8;
     // diagnostics / tests: a wider histogram type than Runner.cpp:75-89 would pick (the
     // 32/64-bit feature paths, with their unsigned wrap-arounds, on small inputs)
     if (const char *fw = getenv("MC_FORCE_WIDTH")) width = std::max(width, atoi(fw));
     rr.width = width;
     if (verbose) printf("Using %d bit histograms\n", 8 * width);
-    check(mc_kmer_build(ctx, opt.k, width), "mc_kmer_build");
+    if (opt.both_strands) check(mc_kmer_build_strands(ctx, opt.k, width, rr.strands), "mc_kmer_build_strands");
+    else check(mc_kmer_build(ctx, opt.k, width), "mc_kmer_build");
   }
   comm_phase(comm, "train");
   TrainerConfig tc;
@@ -318,6 +356,7 @@ RunResult run_pipeline(const Dataset &ds, mc_ctx *ctx, Options opt, bool upload,
   tc.threads = threads;
   tc.verbose = verbose;
   tc.comm = comm;
+  tc.both_strands = opt.both_strands;
   {
     Scope s(rr.timer, "len_order.wait");
     if (len_thread.joinable()) len_thread.join();
@@ -354,6 +393,26 @@ RunResult run_pipeline(const Dataset &ds, mc_ctx *ctx, Options opt, bool upload,
   rr.part = mean_shift_cluster(ds, ctx, *bvp, cc, rr.timer, rr.stats);
   rr.stats.nw_pairs = tr.nw_pairs;
   rr.stats.nw_cells = tr.nw_cells;
+  if (opt.both_strands) {
+    // every member against its centre, grouped by centre (one staged centre row per cluster)
+    Scope s(rr.timer, "orient");
+    std::vector<uint32_t> a, b;
+    for (const Center &c : rr.part)
+      for (uint32_t p : c.points) {
+        a.push_back(p);
+        b.push_back(c.centre);
+      }
+    std::vector<uint8_t> st(a.size(), 0);
+    std::vector<uint64_t> sad(2 * a.size(), 0);
+    check(mc_orient_pairs(ctx, a.data(), b.data(), a.size(), st.data(), sad.data()), "mc_orient_pairs");
+    size_t at = 0;
+    for (const Center &c : rr.part) {
+      rr.member_strand.emplace_back(st.begin() + at, st.begin() + at + c.points.size());
+      rr.member_sad.emplace_back(sad.begin() + 2 * at, sad.begin() + 2 * (at + c.points.size()));
+      at += c.points.size();
+    }
+    for (uint8_t v : st) rr.members_minus += v;
+  }
   rr.timer.add("total_pipeline",
                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return rr;
@@ -373,6 +432,11 @@ std::string stats_json(const RunResult &rr, double parse_ms, double write_ms) {
            (unsigned long long)rr.stats.nw_pairs, (unsigned long long)rr.stats.nw_cells,
            (unsigned long long)rr.stats.align_nw_pairs, (unsigned long long)rr.stats.align_nw_cells);
   o += b;
+  if (rr.strands != 1) {
+    snprintf(b, sizeof b, ", \"strands\": %d, \"k_auto_length\": %llu, \"members_minus\": %llu", rr.strands,
+             (unsigned long long)rr.k_auto_length, (unsigned long long)rr.members_minus);
+    o += b;
+  }
   o += ", \"accum_path\": \"" + rr.stats.accum_path + "\"";
   if (!rr.stats.update_path.empty()) o += ", \"update_path\": \"" + rr.stats.update_path + "\"";
   o += ", \"update_iters_fixed\": " + std::to_string(rr.stats.update_iters_fixed);
@@ -392,6 +456,7 @@ void save_model_files(const Options &opt, const Dataset &ds, const RunResult &rr
     m.k = rr.k;
     m.id = rr.similarity;
     m.align = rr.align ? 1 : 0;
+    m.strands = rr.strands;
     m.cls = rr.cls;
     m.centres = rr.part.size();
     write_model(opt.save_model, m);
@@ -401,6 +466,34 @@ void save_model_files(const Options &opt, const Dataset &ds, const RunResult &rr
     for (const Center &c : rr.part) ids.push_back(c.centre);
     write_fasta(opt.save_centres, ds, ids.data(), ids.size());
   }
+}
+
+void write_strands_file(const std::string &path, const Dataset &ds, const RunResult &rr) {
+  if (rr.strands == 1 || rr.member_strand.size() != rr.part.size()) throw Error("--strands needs a --both-strands run", 1);
+  auto name = [&](uint32_t id) {  // as meshclust-assign's TSV names a read: the header line without '>'
+    const auto h = ds.headers[id];
+    return std::string(h.substr(h.empty() ? 0 : 1));
+  };
+  std::string out;
+  char b[96];
+  int label = 0;
+  for (size_t c = 0; c < rr.part.size(); c++) {
+    const Center &cen = rr.part[c];
+    if (cen.points.empty()) continue;
+    const std::string cname = name(cen.centre);
+    for (size_t j = 0; j < cen.points.size(); j++) {
+      snprintf(b, sizeof b, "\t%d\t", label);
+      out += name(cen.points[j]) + b + cname;
+      snprintf(b, sizeof b, "\t%c\t%llu\t%llu\n", rr.member_strand[c][j] ? '-' : '+',
+               (unsigned long long)rr.member_sad[c][2 * j], (unsigned long long)rr.member_sad[c][2 * j + 1]);
+      out += b;
+    }
+    label++;
+  }
+  FILE *f = fopen(path.c_str(), "w");
+  if (!f) throw Error("cannot write " + path + ": " + strerror(errno));
+  const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+  if (fclose(f) != 0 || !ok) throw Error("cannot write " + path);
 }
 
 static void write_stats(const std::string &path, const RunResult &rr, double parse_ms, double write_ms) {
@@ -554,6 +647,7 @@ int meshclust_main(int argc, char **argv) {
     if (!opt.quiet) printf("Printing output\n");
     write_clstr(opt.output, ds, rr.part, threads);
     save_model_files(opt, ds, rr);
+    if (!opt.strands_file.empty()) write_strands_file(opt.strands_file, ds, rr);
     double write_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     if (!opt.stats_json.empty()) write_stats(opt.stats_json, rr, parse_ms, write_ms);
     mc_ctx_destroy(ctx);

@@ -30,6 +30,10 @@ struct Options {
   std::string stats_json;  // per-phase timings + work counts
   std::string save_model;    // --save-model FILE: k, id, the trained classifier (model.hpp)
   std::string save_centres;  // --save-centres FILE: the final centres as FASTA, cluster order
+  // --both-strands: cluster on canonical rows (row[i] + row[rc(i)] - 1), so a read and its reverse
+  // complement are the same point; --strands FILE: every member's strand against its centre
+  bool both_strands = false;
+  std::string strands_file;
 };
 
 // Parses argv like the reference; bad input throws mc::Error (OptionError in runner.cpp)
@@ -49,7 +53,22 @@ struct RunResult {
   mc_classifier cls{};
   double similarity = 0;
   bool align = false;
+  // --both-strands: strands 3, the doubled mean length the automatic k was computed from, and per
+  // cluster (rr.part order) every member's strand against its centre (mc_orient_pairs: 0 plus,
+  // 1 minus) with sad_plus / sad_minus interleaved
+  int strands = 1;
+  uint64_t k_auto_length = 0, members_minus = 0;
+  std::vector<std::vector<uint8_t>> member_strand;
+  std::vector<std::vector<uint64_t>> member_sad;
 };
+
+// Runner::find_k's formula (Runner.cpp:265-292) on a mean length: ceil(log4(length)) - 1.
+int recommended_k(unsigned long long length);
+
+// --strands FILE of a finished --both-strands run: one line per read in .clstr order,
+// name, cluster, centre name, + or -, sad_plus, sad_minus (tab separated; a name is the header
+// line without '>', as in meshclust-assign's TSV)
+void write_strands_file(const std::string &path, const Dataset &ds, const RunResult &rr);
 
 // --save-model / --save-centres of a finished run (where the .clstr is written; rank 0 only).
 void save_model_files(const Options &opt, const Dataset &ds, const RunResult &rr);

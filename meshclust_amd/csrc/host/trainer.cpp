@@ -92,7 +92,25 @@ void Trainer::nw_batch(const std::vector<PairId> &pairs, std::vector<double> &id
     nw_pairs++;
     nw_cells += ds_.lengths[p.first] * ds_.lengths[p.second];
   }
-  check(mc_nw_identity(ctx_, a.data(), b.data(), pairs.size(), ident.data(), nullptr, nullptr), "mc_nw_identity");
+  if (!cfg_.both_strands) {
+    check(mc_nw_identity(ctx_, a.data(), b.data(), pairs.size(), ident.data(), nullptr, nullptr), "mc_nw_identity");
+    return;
+  }
+  // both strands: the m plus pairs, then the same pairs with a reversed; both alignments count
+  strands_engine_check();
+  const size_t m = pairs.size();
+  for (const auto &p : pairs) {
+    nw_pairs++;
+    nw_cells += ds_.lengths[p.first] * ds_.lengths[p.second];
+  }
+  a.insert(a.end(), a.begin(), a.begin() + m);
+  b.insert(b.end(), b.begin(), b.begin() + m);
+  std::vector<uint8_t> minus(2 * m, 0);
+  std::fill(minus.begin() + m, minus.end(), 1);
+  std::vector<double> both(2 * m, 0.0);
+  check(mc_nw_identity_strands(ctx_, a.data(), b.data(), minus.data(), 2 * m, both.data(), nullptr, nullptr),
+        "mc_nw_identity_strands");
+  for (size_t i = 0; i < m; i++) ident[i] = both[m + i] > both[i] ? both[m + i] : both[i];
 }
 
 // Header order of pair ids (the reference's std::set<pair<Point*, Point*>> comparators order

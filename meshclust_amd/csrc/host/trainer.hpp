@@ -32,6 +32,9 @@ struct TrainerConfig {
   // computed ahead by the caller (Trainer::length_order, overlapping the upload and K1); empty:
   // split computes it
   std::vector<uint32_t> length_order;
+  // meshclust --both-strands: a label is max(identity(a, b), identity(rc(a), b)), both through
+  // mc_nw_identity_strands (a is the operand that is reversed; a tie keeps the plus value)
+  bool both_strands = false;
 };
 
 class Trainer {
@@ -42,6 +45,8 @@ class Trainer {
   // split's first sort: the ids by length, exactly as std::sort leaves them
   static std::vector<uint32_t> length_order(const Dataset &ds, int threads);
   mc_classifier classifier() const { return feat.to_classifier(weights); }
+  // the trainer's only alignment seam: the label identity of every pair (see both_strands)
+  void nw_batch(const std::vector<PairId> &pairs, std::vector<double> &ident);
 
   FeatureSet feat;
   std::vector<double> weights;
@@ -56,7 +61,6 @@ class Trainer {
                   std::vector<std::pair<PairId, double>> &bn);
   Matrix feat_matrix(const std::vector<PairId> &pos, const std::vector<PairId> &neg, int ncols,
                      Matrix &labels);
-  void nw_batch(const std::vector<PairId> &pairs, std::vector<double> &ident);
   // all-gather of `words` u64 per rank (every rank the same count); false: one rank
   bool gather(const std::vector<uint64_t> &mine, std::vector<uint64_t> &all) const;
   bool hdr_less(uint32_t a, uint32_t b) const;
