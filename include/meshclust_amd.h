@@ -353,7 +353,9 @@ int mc_revcomp_sequences(mc_ctx *ctx, const uint32_t *ids, uint64_t m, uint8_t *
  * every result going to its pair's own slot.  A batch ends at MC_IDENT_BATCH_PAIRS pairs or
  * before the read whose string would take the buffer past MC_IDENT_BATCH_BYTES (records padded
  * to 16 bytes; a single longer read still gets its own batch), so the scratch stays bounded for
- * any m.  Environment, read per call: MC_IDENT_BATCH=<pairs> lowers the pair cap.  Batching
+ * any m.  Environment, read per call: MC_IDENT_BATCH=<pairs> lowers the pair cap and
+ * MC_IDENT_BYTES=<bytes> the cap on the buffer of minus-strand strings (the latter also in
+ * mc_revcomp_sequences, mc_nw_align_strands and the pile-ups, which share the buffer).  Batching
  * changes no result.  Errors are mc_nw_identity's: no sequences MC_ERR_STATE, an id >= n
  * MC_ERR_ARG, m = 0 MC_OK.  len/ids may be NULL.  The alignments are timed as "nw", the
  * reverse-complement kernel as "layout" (mc_timers).
@@ -387,8 +389,8 @@ int mc_nw_identity_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, co
  * MC_ALIGN_SCRATCH_BYTES, or where mc_nw_identity_strands' buffer of minus-strand strings would
  * overflow; the context owns the scratch and reuses it.  A pair that alone needs more than the
  * cap is MC_ERR_UNSUPPORTED, checked before any launch, no output written.  Environment, read per
- * call: MC_ALIGN_BATCH=<pairs> and MC_ALIGN_SCRATCH=<bytes> lower the two caps.  Batching changes
- * no result.  m = 0 is MC_OK, no sequences MC_ERR_STATE, an id >= n MC_ERR_ARG.  The forward and
+ * call: MC_ALIGN_BATCH=<pairs> and MC_ALIGN_SCRATCH=<bytes> lower the two caps, MC_IDENT_BYTES=<bytes>
+ * that of the minus-strand strings.  Batching changes no result.  m = 0 is MC_OK, no sequences MC_ERR_STATE, an id >= n MC_ERR_ARG.  The forward and
  * traceback kernels are timed as "nw", the reverse-complement kernel as "layout" (mc_timers).
  * mc_nw_align_profile (a measurement aid): out[0], out[1] = device ms of the forward and of the
  * traceback (+ packing) kernels, out[2] = choice bytes the batches held, since the last reset.

@@ -10,14 +10,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "abi_util.hpp"
 #include "mcgpu.hpp"
 
 namespace mcg {
@@ -114,17 +113,27 @@ static double decision_threshold() {
   return hi;
 }
 
-template <typename T>
-static int upload(mc_ctx *c, Buf &b, const T *h, size_t count, hipStream_t s) {
-  const size_t bytes = count * sizeof(T);
-  if (int rc = ensure(b, bytes + 16)) return rc;
-  if (!count) return MC_OK;
-  // Small inputs (the per-call id lists, offsets, member lists) go through a pinned staging
-  // ring owned by the context: a copy from pinned memory is a plain DMA, a pageable one is
-  // staged by the runtime.  A region is reused only after a stream synchronize that follows
-  // its copy (the ring wraps behind one).
-  static const bool staged = !getenv("MC_PAGEABLE_UPLOADS");
+int check_ids(mc_ctx *c, const uint32_t *ids, uint64_t m) {
+  for (uint64_t i = 0; i < m; i++)
+    if (ids[i] >= c->n) {
+      set_error("point id out of range");
+      return MC_ERR_ARG;
+    }
+  return MC_OK;
+}
+
+uint64_t env_cap(const char *name, uint64_t dflt) {
+  if (const char *e = getenv(name)) {
+    const long long v = atoll(e);
+    if (v > 0 && (uint64_t)v < dflt) return (uint64_t)v;
+  }
+  return dflt;
+}
+
+int stage_copy(mc_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t s, bool sync_pageable) {
+  if (!bytes) return MC_OK;
   constexpr size_t STAGE = 8u << 20, SMALL = 1u << 20;
+  static const bool staged = !getenv("MC_PAGEABLE_UPLOADS");  // (once: every step of a clustering uploads thousands of lists)
   if (staged && bytes <= SMALL) {
     if (!c->h_stage && hipHostMalloc((void **)&c->h_stage, STAGE, hipHostMallocDefault) != hipSuccess) {
       (void)hipGetLastError();
@@ -136,58 +145,21 @@ static int upload(mc_ctx *c, Buf &b, const T *h, size_t count, hipStream_t s) {
         MCG_CHECK(hipStreamSynchronize(s));
         off = 0;
       }
-      memcpy(c->h_stage + off, h, bytes);
-      MCG_CHECK(hipMemcpyAsync(b.p, c->h_stage + off, bytes, hipMemcpyHostToDevice, s));
-      c->stage_off = off + bytes;
-      return MC_OK;
-    }
-  }
-  MCG_CHECK(hipMemcpyAsync(b.p, h, bytes, hipMemcpyHostToDevice, s));
-  return MC_OK;
-}
-
-// launch helpers' small host arrays (nw.hip's bucket lists) through the same pinned ring
-int stage_h2d(mc_ctx *c, void *dst, const void *src, size_t bytes) {
-  if (!bytes) return MC_OK;
-  constexpr size_t STAGE = 8u << 20, SMALL = 1u << 20;
-  if (bytes <= SMALL && !getenv("MC_PAGEABLE_UPLOADS")) {
-    if (!c->h_stage && hipHostMalloc((void **)&c->h_stage, STAGE, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      c->h_stage = nullptr;
-    }
-    if (c->h_stage) {
-      size_t off = (c->stage_off + 255) & ~(size_t)255;
-      if (off + bytes > STAGE) {
-        MCG_CHECK(hipStreamSynchronize(c->stream));
-        off = 0;
-      }
       memcpy(c->h_stage + off, src, bytes);
-      MCG_CHECK(hipMemcpyAsync(dst, c->h_stage + off, bytes, hipMemcpyHostToDevice, c->stream));
+      MCG_CHECK(hipMemcpyAsync(dst, c->h_stage + off, bytes, hipMemcpyHostToDevice, s));
       c->stage_off = off + bytes;
       return MC_OK;
     }
   }
-  MCG_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-  MCG_CHECK(hipStreamSynchronize(c->stream));  // (a pageable source may go out of scope)
+  MCG_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+  if (sync_pageable) MCG_CHECK(hipStreamSynchronize(s));
   return MC_OK;
 }
 
-template <typename T>
-static int download(T *h, const void *d, size_t count, hipStream_t s) {
-  if (count) MCG_CHECK(hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, s));
-  return MC_OK;
-}
+// launch helpers' small host arrays (nw.hip's bucket lists), which may go out of scope
+int stage_h2d(mc_ctx *c, void *dst, const void *src, size_t bytes) { return stage_copy(c, dst, src, bytes, c->stream, true); }
 
-struct DPart {  // one result of a call: `bytes` from device `d` to host `h` (h null: not wanted)
-  void *h;
-  const void *d;
-  size_t bytes;
-};
-static int download_pinned(mc_ctx *c, const void *d, size_t bytes, hipStream_t s, uint8_t **h);
-// A call's results through the pinned landing buffer: one DMA per part into it, one stream
-// synchronize, then the host copies (every part a pageable download was a runtime-staged copy).
-// Ends with the stream synchronized, as the direct downloads it replaces did.
-static int download_parts(mc_ctx *c, std::initializer_list<DPart> parts, hipStream_t s) {
+int download_parts(mc_ctx *c, std::initializer_list<DPart> parts, hipStream_t s) {
   size_t total = 0;
   for (const DPart &p : parts)
     if (p.h && p.bytes) total += (p.bytes + 255) / 256 * 256;
@@ -217,12 +189,7 @@ static int download_parts(mc_ctx *c, std::initializer_list<DPart> parts, hipStre
   return MC_OK;
 }
 
-// One device region of a call's results copied to the context's pinned landing buffer (a plain
-// DMA; a pageable destination is staged by the runtime, one staged copy per download) and the
-// stream synchronized: the caller then copies the parts out of *h.  *h is null only when the
-// landing buffer cannot be allocated (the caller then downloads the parts directly); a failing
-// copy or synchronize is reported as the error it is, with its call site.
-static int download_pinned(mc_ctx *c, const void *d, size_t bytes, hipStream_t s, uint8_t **h) {
+int download_pinned(mc_ctx *c, const void *d, size_t bytes, hipStream_t s, uint8_t **h) {
   *h = nullptr;
   if (bytes > c->h_dstage_cap) {
     if (c->h_dstage) (void)hipHostFree(c->h_dstage);
@@ -247,12 +214,6 @@ static int download_pinned(mc_ctx *c, const void *d, size_t bytes, hipStream_t s
 }  // namespace mcg
 
 using namespace mcg;
-
-#define TRY(x)                  \
-  do {                          \
-    int _rc = (x);              \
-    if (_rc != MC_OK) return _rc; \
-  } while (0)
 
 extern "C" {
 
@@ -564,15 +525,6 @@ int mc_get_histograms(mc_ctx *c, void *hist, uint64_t *mags) {
   return MC_OK;
 }
 
-static int check_ids(mc_ctx *c, const uint32_t *ids, uint64_t m) {
-  for (uint64_t i = 0; i < m; i++)
-    if (ids[i] >= c->n) {
-      set_error("point id out of range");
-      return MC_ERR_ARG;
-    }
-  return MC_OK;
-}
-
 int mc_distance_keys(mc_ctx *c, const uint32_t *pivots, uint32_t npiv, const uint32_t *ids, uint64_t m, uint16_t *keys) {
   if (!c || c->k == 0) return MC_ERR_STATE;
   MCG_CHECK(hipSetDevice(c->device));
@@ -877,465 +829,6 @@ int mc_nw_identity_raw(mc_ctx *c, const uint8_t *a, const uint64_t *a_off, const
   TRY(launch_nw(c, dA, dAo, dI, dB, dBo, dI, m, la, lb, dId, dL, dIds, dSc));
   TRY(download_parts(c, {{ident, dId, m * 8}, {len, dL, m * 4}, {ids, dIds, m * 4}, {score, dSc, m * 4}}, c->stream));
   flush_timers(c);
-  return MC_OK;
-}
-
-// The minus-strand strings (host/revseq.hpp) of the u points ids into c->rc_seq, record r at
-// h_off[r] (filled here: lengths rounded up to 16).  ids go through c->s_h, the offsets through
-// c->s_i; the caller keeps ids and h_off alive until the stream is synchronized.
-static int revseq_batch(mc_ctx *c, const uint32_t *ids, uint32_t u, std::vector<uint64_t> &h_off) {
-  h_off.resize((size_t)u + 1);
-  h_off[0] = 0;
-  for (uint32_t r = 0; r < u; r++)
-    h_off[r + 1] = h_off[r] + (c->h_seq_off[ids[r] + 1] - c->h_seq_off[ids[r]] + 15) / 16 * 16;
-  TRY(ensure(c->rc_seq, h_off[u] + 16));
-  TRY(upload(c, c->s_h, ids, u, c->stream));
-  TRY(upload(c, c->s_i, h_off.data(), (size_t)u + 1, c->stream));
-  return launch_revseq(c, (const uint32_t *)c->s_h.p, u, (const uint64_t *)c->s_i.p, h_off[u], (uint8_t *)c->rc_seq.p);
-}
-
-int mc_revcomp_sequences(mc_ctx *c, const uint32_t *ids, uint64_t m, uint8_t *bytes, uint64_t *off) {
-  if (!c || !c->codes.p) return MC_ERR_STATE;
-  if (!off || (m && !ids)) return MC_ERR_ARG;
-  TRY(check_ids(c, ids, m));
-  off[0] = 0;
-  for (uint64_t i = 0; i < m; i++) off[i + 1] = off[i] + (c->h_seq_off[ids[i] + 1] - c->h_seq_off[ids[i]]);
-  if (!bytes || m == 0) return MC_OK;
-  MCG_CHECK(hipSetDevice(c->device));
-  std::vector<uint64_t> h_off;
-  std::vector<uint8_t> host;
-  for (uint64_t i0 = 0; i0 < m;) {  // batches of at most MC_IDENT_BATCH_BYTES of padded strings
-    uint64_t i1 = i0, pad = 0;
-    while (i1 < m && i1 - i0 < MC_IDENT_BATCH_PAIRS) {
-      const uint64_t need = (off[i1 + 1] - off[i1] + 15) / 16 * 16;
-      if (i1 > i0 && pad + need > MC_IDENT_BATCH_BYTES) break;
-      pad += need;
-      i1++;
-    }
-    TRY(revseq_batch(c, ids + i0, (uint32_t)(i1 - i0), h_off));
-    host.resize(pad);
-    if (pad) MCG_CHECK(hipMemcpyAsync(host.data(), c->rc_seq.p, pad, hipMemcpyDeviceToHost, c->stream));
-    MCG_CHECK(hipStreamSynchronize(c->stream));
-    for (uint64_t i = i0; i < i1; i++)
-      if (off[i + 1] > off[i]) memcpy(bytes + off[i], host.data() + h_off[i - i0], off[i + 1] - off[i]);
-    i0 = i1;
-  }
-  flush_timers(c);
-  return MC_OK;
-}
-
-int mc_nw_identity_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
-                           double *ident, int32_t *len, int32_t *ids) {
-  if (!c || !c->codes.p) return MC_ERR_STATE;
-  if (m == 0) return MC_OK;
-  MCG_CHECK(hipSetDevice(c->device));
-  TRY(check_ids(c, a, m));
-  TRY(check_ids(c, b, m));
-  uint64_t cap = MC_IDENT_BATCH_PAIRS;
-  if (const char *e = getenv("MC_IDENT_BATCH")) {  // (read per call: a test forces several batches)
-    const long long v = atoll(e);
-    if (v > 0 && (uint64_t)v < cap) cap = (uint64_t)v;
-  }
-  auto length = [&](uint32_t id) { return c->h_seq_off[id + 1] - c->h_seq_off[id]; };
-  constexpr uint32_t NO_SLOT = 0xffffffffu;
-  std::vector<uint32_t> slot;  // point id -> its string's slot in this batch's buffer
-  if (a_minus) slot.assign(c->n, NO_SLOT);
-  std::vector<uint32_t> uniq, ai, bi, out;
-  std::vector<uint64_t> h_off, a_off2, la[2], lb[2];
-  for (uint64_t i0 = 0; i0 < m;) {
-    // the batch [i0, i1): ends at the pair cap, or where one more read's string would not fit
-    uniq.clear();
-    uint64_t i1 = i0, pad = 0, nm = 0;
-    while (i1 < m && i1 - i0 < cap) {
-      if (a_minus && a_minus[i1]) {
-        if (slot[a[i1]] == NO_SLOT) {
-          const uint64_t need = (length(a[i1]) + 15) / 16 * 16;
-          if (!uniq.empty() && pad + need > MC_IDENT_BATCH_BYTES) break;
-          pad += need;
-          slot[a[i1]] = (uint32_t)uniq.size();
-          uniq.push_back(a[i1]);
-        }
-        nm++;
-      }
-      i1++;
-    }
-    const uint64_t mb = i1 - i0, np = mb - nm;
-    // the minus pairs first, then the plus pairs; every result goes to its pair's own slot
-    ai.resize(mb);
-    bi.resize(mb);
-    out.resize(mb);
-    for (int s = 0; s < 2; s++) {
-      la[s].clear();
-      lb[s].clear();
-    }
-    uint64_t km = 0, kp = nm;
-    for (uint64_t i = i0; i < i1; i++) {
-      const bool minus = a_minus && a_minus[i];
-      const uint64_t k = minus ? km++ : kp++;
-      ai[k] = minus ? 2 * slot[a[i]] : a[i];  // (the strings' offsets come in [start, end) pairs)
-      bi[k] = b[i];
-      out[k] = (uint32_t)(i - i0);
-      la[minus].push_back(length(a[i]));
-      lb[minus].push_back(length(b[i]));
-    }
-    if (nm) {
-      TRY(revseq_batch(c, uniq.data(), (uint32_t)uniq.size(), h_off));
-      a_off2.resize(2 * uniq.size());
-      for (size_t r = 0; r < uniq.size(); r++) {
-        a_off2[2 * r] = h_off[r];
-        a_off2[2 * r + 1] = h_off[r] + length(uniq[r]);
-        slot[uniq[r]] = NO_SLOT;
-      }
-      TRY(upload(c, c->s_j, a_off2.data(), a_off2.size(), c->stream));
-    }
-    TRY(upload(c, c->s_d, ai.data(), mb, c->stream));
-    TRY(upload(c, c->s_e, bi.data(), mb, c->stream));
-    TRY(upload(c, c->s_g, out.data(), mb, c->stream));
-    TRY(ensure(c->s_f, mb * 16 + 64));
-    double *d_id = (double *)c->s_f.p;
-    int32_t *d_len = (int32_t *)(d_id + mb), *d_ids = d_len + mb;
-    const uint32_t *d_ai = (const uint32_t *)c->s_d.p, *d_bi = (const uint32_t *)c->s_e.p, *d_out = (const uint32_t *)c->s_g.p;
-    if (nm)
-      TRY(launch_nw(c, (uint8_t *)c->rc_seq.p, (uint64_t *)c->s_j.p, d_ai, (uint8_t *)c->codes.p, (uint64_t *)c->seq_off.p, d_bi,
-                    nm, la[1], lb[1], d_id, d_len, d_ids, nullptr, d_out));
-    if (np)
-      TRY(launch_nw(c, (uint8_t *)c->codes.p, (uint64_t *)c->seq_off.p, d_ai + nm, (uint8_t *)c->codes.p,
-                    (uint64_t *)c->seq_off.p, d_bi + nm, np, la[0], lb[0], d_id, d_len, d_ids, nullptr, d_out + nm));
-    TRY(download_parts(c, {{ident ? ident + i0 : nullptr, d_id, mb * 8}, {len ? len + i0 : nullptr, d_len, mb * 4},
-                           {ids ? ids + i0 : nullptr, d_ids, mb * 4}}, c->stream));
-    i0 = i1;
-  }
-  flush_timers(c);
-  return MC_OK;
-}
-
-// The pairs of mc_nw_align_strands / mc_nw_pileup_strands in batches: the forward pass and the
-// traceback of every batch, then per_batch(i0, mb, res) with the batch's TRACE_RES ints per pair
-// on the host; the batch's pair records, operation words and results are still in c->tr_pairs,
-// c->tr_ops and c->tr_res, its minus-strand strings in c->rc_seq.  `who` names the caller in errors.
-static int align_batches(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
-                         const std::function<int(uint64_t, uint64_t, const std::vector<int32_t> &)> &per_batch) {
-  uint64_t pair_cap = MC_ALIGN_BATCH_PAIRS, scr_cap = MC_ALIGN_SCRATCH_BYTES;
-  if (const char *e = getenv("MC_ALIGN_BATCH")) {  // (read per call: the tests put batch ends inside small lists)
-    const long long v = atoll(e);
-    if (v > 0 && (uint64_t)v < pair_cap) pair_cap = (uint64_t)v;
-  }
-  if (const char *e = getenv("MC_ALIGN_SCRATCH")) {
-    const long long v = atoll(e);
-    if (v > 0 && (uint64_t)v < scr_cap) scr_cap = (uint64_t)v;
-  }
-  auto length = [&](uint32_t id) { return c->h_seq_off[id + 1] - c->h_seq_off[id]; };
-  constexpr uint32_t NO_SLOT = 0xffffffffu;
-  std::vector<uint32_t> slot;  // point id -> its minus-strand string's slot in this batch's buffer
-  if (a_minus) slot.assign(c->n, NO_SLOT);
-  std::vector<uint32_t> uniq;
-  std::vector<uint64_t> h_off;
-  std::vector<TracePair> pairs;
-  std::vector<int32_t> res;
-  TRY(ensure(c->tr_err, 256));
-  for (uint64_t i0 = 0; i0 < m;) {
-    // the batch [i0, i1): ends at the pair cap, before the pair that would take the choice
-    // scratch past its cap, or where one more minus read's string would not fit (as
-    // mc_nw_identity_strands)
-    uniq.clear();
-    pairs.clear();
-    uint64_t i1 = i0, pad = 0, chb = 0, bnd = 0, opw = 0;
-    while (i1 < m && i1 - i0 < pair_cap) {
-      const uint64_t la = length(a[i1]), lb = length(b[i1]);
-      const uint64_t need = nw_trace_choice_bytes(la, lb);
-      if (i1 > i0 && chb + need > scr_cap) break;
-      const bool minus = a_minus && a_minus[i1];
-      if (minus && slot[a[i1]] == NO_SLOT) {
-        const uint64_t bytes = (la + 15) / 16 * 16;
-        if (!uniq.empty() && pad + bytes > MC_IDENT_BATCH_BYTES) break;
-        pad += bytes;
-        slot[a[i1]] = (uint32_t)uniq.size();
-        uniq.push_back(a[i1]);
-      }
-      TracePair pr;
-      pr.a_off = minus ? slot[a[i1]] : c->h_seq_off[a[i1]];  // (a minus pair: its slot, made an offset below)
-      pr.b_off = c->h_seq_off[b[i1]];
-      pr.ch_off = chb;
-      pr.bnd_off = bnd;
-      pr.ops_off = opw;
-      pr.la = (uint32_t)la;
-      pr.lb = (uint32_t)lb;
-      pr.a_rc = minus ? 1 : 0;
-      pr.r = (uint32_t)nw_trace_rows(la);
-      pairs.push_back(pr);
-      chb += need;
-      if (la > 64ull * pr.r) bnd += 3 * (lb + 1);
-      opw += la + lb;
-      i1++;
-    }
-    const uint64_t mb = i1 - i0;
-    if (!uniq.empty()) {
-      TRY(revseq_batch(c, uniq.data(), (uint32_t)uniq.size(), h_off));
-      for (TracePair &pr : pairs)
-        if (pr.a_rc) pr.a_off = h_off[pr.a_off];
-      for (uint32_t id : uniq) slot[id] = NO_SLOT;
-    }
-    TRY(ensure(c->tr_choice, chb + 64));
-    TRY(ensure(c->tr_bnd, bnd * 4 + 64));
-    TRY(ensure(c->tr_ops, opw * 4 + 64));
-    TRY(ensure(c->tr_res, mb * TRACE_RES * 4 + 64));
-    TRY(upload(c, c->tr_pairs, pairs.data(), mb, c->stream));
-    TRY(launch_nw_trace(c, pairs, (const TracePair *)c->tr_pairs.p, (const uint8_t *)c->rc_seq.p, (uint8_t *)c->tr_choice.p,
-                        (int *)c->tr_bnd.p, (uint32_t *)c->tr_ops.p, (int32_t *)c->tr_res.p, (int *)c->tr_err.p));
-    c->tr_choice_bytes += (double)chb;
-    res.resize(mb * TRACE_RES);
-    int herr = 0;
-    TRY(download_parts(c, {{res.data(), c->tr_res.p, mb * TRACE_RES * 4}, {&herr, c->tr_err.p, 4}}, c->stream));
-    if (herr) {
-      set_error(std::string(who) + ": a traceback did not reach the matrix's edge within la + lb steps");
-      return MC_ERR_HIP;
-    }
-    TRY(per_batch(i0, mb, res));
-    i0 = i1;
-  }
-  return MC_OK;
-}
-
-// before any launch, and before any output is written: a pair that alone exceeds the scratch cap
-static int align_check_caps(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t *b, uint64_t m) {
-  uint64_t scr_cap = MC_ALIGN_SCRATCH_BYTES;
-  if (const char *e = getenv("MC_ALIGN_SCRATCH")) {
-    const long long v = atoll(e);
-    if (v > 0 && (uint64_t)v < scr_cap) scr_cap = (uint64_t)v;
-  }
-  auto length = [&](uint32_t id) { return c->h_seq_off[id + 1] - c->h_seq_off[id]; };
-  for (uint64_t i = 0; i < m; i++) {
-    const uint64_t la = length(a[i]), lb = length(b[i]);
-    if (la + lb >= (1ull << 27) || nw_trace_choice_bytes(la, lb) > scr_cap) {
-      set_error(std::string(who) + ": pair " + std::to_string(i) + " (" + std::to_string(la) + " x " + std::to_string(lb) +
-                ") needs " + std::to_string(nw_trace_choice_bytes(la, lb)) + " bytes of choices, the cap is " +
-                std::to_string(scr_cap));
-      return MC_ERR_UNSUPPORTED;
-    }
-  }
-  return MC_OK;
-}
-
-int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
-                        uint32_t *cigar, uint64_t cap, uint64_t *cig_off, int32_t *score, int32_t *len, int32_t *ids) {
-  if (!c || !c->codes.p) return MC_ERR_STATE;
-  if (!cig_off) return MC_ERR_ARG;
-  if (m == 0) {
-    cig_off[0] = 0;
-    return MC_OK;
-  }
-  if (!a || !b) return MC_ERR_ARG;
-  MCG_CHECK(hipSetDevice(c->device));
-  TRY(check_ids(c, a, m));
-  TRY(check_ids(c, b, m));
-  TRY(align_check_caps(c, "mc_nw_align_strands", a, b, m));
-  std::vector<uint32_t> words, nops(m);
-  std::vector<uint64_t> dst;
-  TRY(align_batches(c, "mc_nw_align_strands", a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
-    dst.resize(mb);
-    uint64_t tot = 0;
-    for (uint64_t k = 0; k < mb; k++) {
-      dst[k] = tot;
-      nops[i0 + k] = (uint32_t)res[k * TRACE_RES + 3];
-      tot += nops[i0 + k];
-      if (score) score[i0 + k] = res[k * TRACE_RES];
-      if (len) len[i0 + k] = res[k * TRACE_RES + 1];
-      if (ids) ids[i0 + k] = res[k * TRACE_RES + 2];
-    }
-    if (cigar && tot) {  // the batch's words, packed on the device, kept until the whole count is known
-      TRY(ensure(c->tr_out, tot * 4 + 64));
-      TRY(upload(c, c->tr_dst, dst.data(), mb, c->stream));
-      TRY(launch_nw_pack(c, (uint32_t)mb, (const TracePair *)c->tr_pairs.p, (const uint32_t *)c->tr_ops.p,
-                         (const int32_t *)c->tr_res.p, (const uint64_t *)c->tr_dst.p, (uint32_t *)c->tr_out.p));
-      const size_t at = words.size();
-      words.resize(at + tot);
-      MCG_CHECK(hipMemcpyAsync(words.data() + at, c->tr_out.p, tot * 4, hipMemcpyDeviceToHost, c->stream));
-      MCG_CHECK(hipStreamSynchronize(c->stream));
-    }
-    return (int)MC_OK;
-  }));
-  flush_timers(c);
-  cig_off[0] = 0;
-  for (uint64_t i = 0; i < m; i++) cig_off[i + 1] = cig_off[i] + nops[i];
-  if (cigar) {
-    if (cap < cig_off[m]) {
-      set_error("mc_nw_align_strands: cigar holds " + std::to_string(cap) + " words, the alignments have " +
-                std::to_string(cig_off[m]));
-      return MC_ERR_ARG;
-    }
-    if (!words.empty()) memcpy(cigar, words.data(), words.size() * 4);
-  }
-  return MC_OK;
-}
-
-// mc_nw_pileup_strands (weighted false, wtable NULL) and mc_nw_qpileup_strands (weighted: the
-// same call with nwt_qpileup_kernel in place of nwt_pileup_kernel and a second table)
-static int pileup_call(mc_ctx *c, const std::string &who, bool weighted, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus,
-                       uint64_t m, const uint32_t *targets, uint32_t nt, uint64_t *row_off, uint32_t *table, uint32_t *wtable,
-                       uint64_t cap_rows, int32_t *score, int32_t *len, int32_t *ids) {
-  if (!c || !c->codes.p) return MC_ERR_STATE;
-  if (weighted && !c->has_qual) {
-    set_error(who + ": no qualities are loaded (mc_load_qualities)");
-    return MC_ERR_STATE;
-  }
-  if (!row_off || (nt && !targets) || (m && (!a || !b))) return MC_ERR_ARG;
-  if (weighted && !table != !wtable) {
-    set_error(who + ": table and wtable are given together (both NULL: the offsets only)");
-    return MC_ERR_ARG;
-  }
-  MCG_CHECK(hipSetDevice(c->device));
-  TRY(check_ids(c, targets, nt));
-  TRY(check_ids(c, a, m));
-  TRY(check_ids(c, b, m));
-  constexpr uint32_t NO_TARGET = 0xffffffffu;
-  std::vector<uint32_t> tindex(c->n, NO_TARGET);  // point id -> its place among the targets
-  for (uint32_t t = 0; t < nt; t++) {
-    if (tindex[targets[t]] != NO_TARGET) {
-      set_error(who + ": point " + std::to_string(targets[t]) + " is listed twice among the targets");
-      return MC_ERR_ARG;
-    }
-    tindex[targets[t]] = t;
-  }
-  for (uint64_t i = 0; i < m; i++)
-    if (tindex[b[i]] == NO_TARGET) {
-      set_error(who + ": pair " + std::to_string(i) + "'s seq2, point " + std::to_string(b[i]) +
-                ", is not among the targets");
-      return MC_ERR_ARG;
-    }
-  if (weighted) {  // a column's weight is at most MC_QUAL_MAX per pair: the sums must fit 32 bits
-    std::vector<uint64_t> npairs(nt, 0);
-    for (uint64_t i = 0; i < m; i++)
-      if (++npairs[tindex[b[i]]] > 0xffffffffull / MC_QUAL_MAX) {
-        set_error(who + ": target " + std::to_string(b[i]) + " receives more than " + std::to_string(0xffffffffull / MC_QUAL_MAX) +
-                  " pairs, its weights would not fit 32 bits");
-        return MC_ERR_ARG;
-      }
-  }
-  TRY(align_check_caps(c, who.c_str(), a, b, m));
-  std::vector<uint64_t> toff(nt);
-  row_off[0] = 0;
-  for (uint32_t t = 0; t < nt; t++) {
-    toff[t] = c->h_seq_off[targets[t]];
-    row_off[t + 1] = row_off[t] + (c->h_seq_off[targets[t] + 1] - c->h_seq_off[targets[t]]) + 1;
-  }
-  if (!table) return MC_OK;
-  const uint64_t rows = row_off[nt];
-  if (cap_rows < rows) {
-    set_error(who + ": table holds " + std::to_string(cap_rows) + " rows, the targets have " + std::to_string(rows));
-    return MC_ERR_ARG;
-  }
-  if (rows == 0) return MC_OK;
-  if (m == 0) {
-    memset(table, 0, rows * MC_PILEUP_CH * 4);
-    if (weighted) memset(wtable, 0, rows * MC_PILEUP_CH * 4);
-    return MC_OK;
-  }
-  // the table and the two difference arrays stay on the device for the whole call: zeroed once,
-  // every batch adds to them, one download at the end
-  TRY(ensure(c->pu_table, rows * MC_PILEUP_CH * 4 + 64));
-  TRY(ensure(c->pu_diff, rows * 8 + 64));
-  uint32_t *d_table = (uint32_t *)c->pu_table.p;
-  int32_t *d_deq = (int32_t *)c->pu_diff.p, *d_ddel = d_deq + rows;
-  MCG_CHECK(hipMemsetAsync(d_table, 0, rows * MC_PILEUP_CH * 4, c->stream));
-  MCG_CHECK(hipMemsetAsync(d_deq, 0, rows * 8, c->stream));
-  uint32_t *d_wtable = nullptr;
-  if (weighted) {
-    TRY(ensure(c->pu_wtable, rows * MC_PILEUP_CH * 4 + 64));
-    d_wtable = (uint32_t *)c->pu_wtable.p;
-    MCG_CHECK(hipMemsetAsync(d_wtable, 0, rows * MC_PILEUP_CH * 4, c->stream));
-  }
-  const char *nv = getenv("MC_PILEUP_NAIVE");  // (a measurement aid: an atomic per column; the same table)
-  const bool naive = nv && atoi(nv) != 0;
-  std::vector<uint64_t> rowbase, qoff;
-  TRY(align_batches(c, who.c_str(), a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
-    rowbase.resize(mb);
-    for (uint64_t k = 0; k < mb; k++) {
-      rowbase[k] = row_off[tindex[b[i0 + k]]];
-      if (score) score[i0 + k] = res[k * TRACE_RES];
-      if (len) len[i0 + k] = res[k * TRACE_RES + 1];
-      if (ids) ids[i0 + k] = res[k * TRACE_RES + 2];
-    }
-    TRY(upload(c, c->pu_rows, rowbase.data(), mb, c->stream));
-    if (weighted) {
-      qoff.resize(mb);
-      for (uint64_t k = 0; k < mb; k++) qoff[k] = c->h_seq_off[a[i0 + k]];
-      TRY(upload(c, c->pu_qoff, qoff.data(), mb, c->stream));
-      return launch_nw_qpileup(c, (uint32_t)mb, (const TracePair *)c->tr_pairs.p, (const uint8_t *)c->rc_seq.p,
-                               (const uint32_t *)c->tr_ops.p, (const int32_t *)c->tr_res.p, (const uint64_t *)c->pu_rows.p,
-                               (const uint64_t *)c->pu_qoff.p, d_table, d_wtable, d_deq, d_ddel);
-    }
-    return launch_nw_pileup(c, (uint32_t)mb, (const TracePair *)c->tr_pairs.p, (const uint8_t *)c->rc_seq.p,
-                            (const uint32_t *)c->tr_ops.p, (const int32_t *)c->tr_res.p, (const uint64_t *)c->pu_rows.p, d_table,
-                            d_deq, d_ddel, naive);
-  }));
-  TRY(upload(c, c->pu_toff, toff.data(), nt, c->stream));
-  TRY(upload(c, c->pu_roff, row_off, (size_t)nt + 1, c->stream));
-  TRY(launch_nw_pileup_finish(c, nt, (const uint64_t *)c->pu_toff.p, (const uint64_t *)c->pu_roff.p, d_table, d_deq, d_ddel));
-  MCG_CHECK(hipMemcpyAsync(table, d_table, rows * MC_PILEUP_CH * 4, hipMemcpyDeviceToHost, c->stream));
-  if (weighted) MCG_CHECK(hipMemcpyAsync(wtable, d_wtable, rows * MC_PILEUP_CH * 4, hipMemcpyDeviceToHost, c->stream));
-  MCG_CHECK(hipStreamSynchronize(c->stream));
-  flush_timers(c);
-  return MC_OK;
-}
-
-int mc_nw_pileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
-                         const uint32_t *targets, uint32_t nt, uint64_t *row_off, uint32_t *table, uint64_t cap_rows,
-                         int32_t *score, int32_t *len, int32_t *ids) {
-  return pileup_call(c, "mc_nw_pileup_strands", false, a, b, a_minus, m, targets, nt, row_off, table, nullptr, cap_rows, score, len,
-                     ids);
-}
-
-int mc_nw_qpileup_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
-                          const uint32_t *targets, uint32_t nt, uint64_t *row_off, uint32_t *table, uint32_t *wtable,
-                          uint64_t cap_rows, int32_t *score, int32_t *len, int32_t *ids) {
-  return pileup_call(c, "mc_nw_qpileup_strands", true, a, b, a_minus, m, targets, nt, row_off, table, wtable, cap_rows, score, len,
-                     ids);
-}
-
-// A Phred value (0 .. MC_QUAL_MAX) per byte of the loaded sequences, at their offsets.
-int mc_load_qualities(mc_ctx *c, const uint8_t *qual, uint64_t bytes) {
-  if (!c || !c->codes.p) return MC_ERR_STATE;
-  const uint64_t want = c->h_seq_off.empty() ? 0 : c->h_seq_off.back();
-  if (bytes != want || (bytes && !qual)) {
-    set_error("mc_load_qualities: " + std::to_string(bytes) + " values, the loaded sequences have " + std::to_string(want) + " bytes");
-    return MC_ERR_ARG;
-  }
-  for (uint64_t i = 0; i < bytes; i++)
-    if (qual[i] > MC_QUAL_MAX) {
-      set_error("mc_load_qualities: value " + std::to_string((int)qual[i]) + " at byte " + std::to_string(i) + " is above MC_QUAL_MAX");
-      return MC_ERR_ARG;
-    }
-  MCG_CHECK(hipSetDevice(c->device));
-  TRY(ensure(c->qual, bytes + 64));
-  if (bytes) MCG_CHECK(hipMemcpyAsync(c->qual.p, qual, bytes, hipMemcpyHostToDevice, c->stream));
-  MCG_CHECK(hipStreamSynchronize(c->stream));
-  c->has_qual = true;
-  return MC_OK;
-}
-
-int mc_nw_align_profile(mc_ctx *c, double *out, int reset) {
-  if (!c || !out) return MC_ERR_ARG;
-  (void)hipStreamSynchronize(c->stream);
-  flush_timers(c);
-  out[0] = c->fam_ms[F_NW_FWD];
-  out[1] = c->fam_ms[F_NW_TB];
-  out[2] = c->tr_choice_bytes;
-  if (reset) {
-    c->fam_ms[F_NW_FWD] = c->fam_ms[F_NW_TB] = c->fam_n[F_NW_FWD] = c->fam_n[F_NW_TB] = 0;
-    c->tr_choice_bytes = 0;
-  }
-  return MC_OK;
-}
-
-int mc_nw_pileup_profile(mc_ctx *c, double *out, int reset) {
-  if (!c || !out) return MC_ERR_ARG;
-  (void)hipStreamSynchronize(c->stream);
-  flush_timers(c);
-  out[0] = c->fam_ms[F_NW_FWD];
-  out[1] = c->fam_ms[F_NW_TB];
-  out[2] = c->fam_ms[F_NW_PU];
-  if (reset)
-    for (int f : {F_NW_FWD, F_NW_TB, F_NW_PU}) c->fam_ms[f] = c->fam_n[f] = 0;
   return MC_OK;
 }
 

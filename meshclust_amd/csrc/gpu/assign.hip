@@ -42,6 +42,7 @@
 
 #include "../host/strand.hpp"
 #include "../host/topk.hpp"
+#include "abi_util.hpp"
 #include "features.hpp"
 
 namespace mcg {
@@ -500,16 +501,8 @@ int assign_impl(mc_ctx *c, const char *who, const uint32_t *centre_ids, uint32_t
     set_error(w + ": no centres (or no query ids)");
     return MC_ERR_ARG;
   }
-  for (uint32_t j = 0; j < C; j++)
-    if (centre_ids[j] >= c->n) {
-      set_error("point id out of range");
-      return MC_ERR_ARG;
-    }
-  for (uint64_t i = 0; i < M; i++)
-    if (query_ids[i] >= c->n) {
-      set_error("point id out of range");
-      return MC_ERR_ARG;
-    }
+  TRY(check_ids(c, centre_ids, C));
+  TRY(check_ids(c, query_ids, M));
   if (stats) stats[0] = stats[1] = stats[2] = 0;
   if (M == 0) return MC_OK;
   const bool both = strands == (MC_STRAND_PLUS | MC_STRAND_MINUS);
@@ -538,9 +531,9 @@ int assign_impl(mc_ctx *c, const char *who, const uint32_t *centre_ids, uint32_t
       gate[C + j] = (uint64_t)(len / sim);
     }
   const size_t res_off = ((size_t)M * 4 + 15) / 16 * 16;  // s_f: best, n_similar, then the two counters
-  if (int rc = ensure(c->s_a, (size_t)C * 4 + 16)) return rc;
-  if (int rc = ensure(c->s_b, (size_t)M * 4 + 16)) return rc;
-  if (int rc = ensure(c->s_c, (size_t)C * 16 + 16)) return rc;
+  TRY(upload(c, c->s_a, centre_ids, C, c->stream));
+  TRY(upload(c, c->s_b, query_ids, (size_t)M, c->stream));
+  TRY(upload(c, c->s_c, gate.data(), gate.size(), c->stream));
   if (int rc = ensure(c->s_e, (size_t)M * 8 + 16)) return rc;
   if (int rc = ensure(c->s_f, 2 * res_off + 64)) return rc;
   AssignArgs A;
@@ -586,9 +579,6 @@ int assign_impl(mc_ctx *c, const char *who, const uint32_t *centre_ids, uint32_t
     A.strand = (uint8_t *)c->s_g.p + 2 * res_off;
     A.bval_m = (double *)c->s_h.p;
   }
-  MCG_CHECK(hipMemcpyAsync(c->s_a.p, centre_ids, (size_t)C * 4, hipMemcpyHostToDevice, c->stream));
-  MCG_CHECK(hipMemcpyAsync(c->s_b.p, query_ids, (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
-  MCG_CHECK(hipMemcpyAsync(c->s_c.p, gate.data(), (size_t)C * 16, hipMemcpyHostToDevice, c->stream));
   MCG_CHECK(hipMemsetAsync(A.stats, 0, 16, c->stream));
   const size_t lds = (size_t)tile * ent_bytes;
   MCG_CHECK(hipEventRecord(c->ev0, c->stream));
@@ -677,16 +667,11 @@ extern "C" int mc_revcomp_rows(mc_ctx *c, const uint32_t *ids, uint64_t m, void 
     set_error("mc_revcomp_rows: no ids (or no output)");
     return MC_ERR_ARG;
   }
-  for (uint64_t i = 0; i < m; i++)
-    if (ids[i] >= c->n) {
-      set_error("point id out of range");
-      return MC_ERR_ARG;
-    }
+  TRY(check_ids(c, ids, m));
   if (m == 0) return MC_OK;
   MCG_CHECK(hipSetDevice(c->device));
-  if (int rc = ensure(c->s_a, (size_t)m * 4 + 16)) return rc;
-  if (int rc = ensure(c->s_d, (size_t)m * H.pitch + 16)) return rc;
-  MCG_CHECK(hipMemcpyAsync(c->s_a.p, ids, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+  TRY(upload(c, c->s_a, ids, (size_t)m, c->stream));
+  TRY(ensure(c->s_d, (size_t)m * H.pitch + 16));
   if (int rc = launch_revcomp(c, H, (const uint32_t *)c->s_a.p, m, (uint8_t *)c->s_d.p)) return rc;
   const size_t rowb = (size_t)H.B * H.width;
   MCG_CHECK(hipMemcpy2DAsync(rows, rowb, c->s_d.p, H.pitch, rowb, m, hipMemcpyDeviceToHost, c->stream));

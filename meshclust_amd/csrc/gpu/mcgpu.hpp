@@ -116,8 +116,8 @@ struct HostScan {
 struct mc_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  uint8_t *h_stage = nullptr;  // pinned staging ring for small uploads (abi.hip upload)
-  uint8_t *h_dstage = nullptr;  // pinned landing buffer for a call's results (abi.hip download_pinned)
+  uint8_t *h_stage = nullptr;  // pinned staging ring for small uploads (abi_util.hpp stage_copy)
+  uint8_t *h_dstage = nullptr;  // pinned landing buffer for a call's results (abi_util.hpp download_pinned)
   size_t h_dstage_cap = 0;
   size_t stage_off = 0;
   // sequences
@@ -231,7 +231,7 @@ int split_build_words(mc_ctx *c, const uint32_t *d_order, uint64_t n, uint32_t n
 int launch_order_members(mc_ctx *c, const uint64_t *d_keys, const uint32_t *d_pos, const uint64_t *d_cl_off, uint64_t ncl,
                          uint32_t *d_ids);
 uint64_t order_members_max();
-// a small host array to device memory through the context's pinned staging ring (abi.hip)
+// a small host array to device memory through the context's pinned staging ring (abi_util.hpp stage_copy)
 int stage_h2d(mc_ctx *c, void *dst, const void *src, size_t bytes);
 int launch_select(mc_ctx *c, uint64_t *d_words, uint64_t n, uint32_t *d_scr, SplitNode *d_nodes, int32_t *d_nnodes,
                   int32_t maxnode, int32_t depth0, uint32_t ngroups, const uint32_t *d_qarr, const uint64_t *d_qoff,

@@ -43,6 +43,10 @@ struct PileArgs {
   uint32_t *table;
   int32_t *deq, *ddel;
   uint32_t npairs;
+  // the weighted kernel only (null elsewhere, and never read)
+  const uint8_t *qual;   // the loaded qualities, at the sequences' offsets
+  const uint64_t *qoff;  // per pair: the offset of its read (as loaded, whatever the strand)
+  uint32_t *wtable;
 };
 
 __device__ __forceinline__ uint32_t wave_scan(uint32_t v, int lane) {  // inclusive prefix sum over the wave
@@ -56,19 +60,49 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t v, int lane) {  // inclus
 
 __device__ __forceinline__ uint32_t base_channel(uint8_t x) { return x <= 3 ? x : 4u; }
 
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d, 64));
+  return v;
+}
+
 // NAIVE: every column of an '=' or 'D' run gets its own atomic too (the form the difference arrays
-// are measured against; the same table)
-template <bool NAIVE>
+// are measured against; the same table).
+//
+// WEIGHTED: the pile-up with quality weights (mc_nw_qpileup_strands).  The same
+// counts (the same difference arrays, per-column atomics and finish kernel) and, beside them, a
+// second table of the same shape that receives the read's Phred values.  Qs(i), the quality of base
+// i of seq1 as aligned, is qual[qoff + i] of a plus pair and qual[qoff + la - 1 - i] of a minus
+// pair: an index, the qualities are never reversed in memory.
+//   '=' / 'X' at (i, j)   wtable[j + t][channel of a[i + t]] += Qs(i + t) for every column of the run
+//   'D' of n at (i, j)    channel 5 of rows j .. j + n - 1 += min(Qs(i - 1) if i > 0, Qs(i) if i < la)
+//   'I' of n at (i, j)    channel 6 of row j += min Qs(i .. i + n - 1)
+// Every column carries its own value, so no difference array serves: a lane walks a run of at most
+// SPREAD columns itself, longer runs are taken one after the other by the whole wave, 64 columns
+// (consecutive quality bytes, consecutive rows) per step; a long 'I' run's minimum is a wave
+// minimum.  A zero weight issues no atomic.  (There is no naive weighted form.)
+template <bool NAIVE, bool WEIGHTED>
 __global__ __launch_bounds__(64) void nwt_pileup_kernel(PileArgs q) {
+  static_assert(!(NAIVE && WEIGHTED), "the naive form has no weights");
   const uint32_t p = blockIdx.x;
   if (p >= q.npairs) return;
   const TracePair pr = q.pairs[p];
   const uint32_t nw = (uint32_t)q.res[(uint64_t)p * TRACE_RES + 3], cap = pr.la + pr.lb;
   if (nw == 0 || nw > cap) return;
   const uint8_t *a = (pr.a_rc ? q.rc : q.codes) + pr.a_off;
+  const uint8_t *ql = WEIGHTED ? q.qual + q.qoff[p] : nullptr;
+  const uint32_t la = pr.la;
+  const bool rc = pr.a_rc != 0;
+  auto Qs = [&](uint32_t i) -> uint32_t { return ql[rc ? la - 1 - i : i]; };  // i < la
+  auto gapq = [&](uint32_t i) -> uint32_t {  // the weight of a 'D' run with i read bases before it
+    uint32_t v = 0xffffffffu;
+    if (i > 0) v = Qs(i - 1);
+    if (i < la) v = min(v, Qs(i));
+    return v == 0xffffffffu ? 0u : v;
+  };
   const uint32_t *src = q.ops + pr.ops_off + (cap - nw);
   const uint64_t row0 = q.rowbase[p];
-  uint32_t *tab = q.table + row0 * MC_PILEUP_CH;
+  uint32_t *tab = q.table + row0 * MC_PILEUP_CH, *wt = WEIGHTED ? q.wtable + row0 * MC_PILEUP_CH : nullptr;
   int32_t *deq = q.deq + row0, *ddel = q.ddel + row0;
   const int lane = (int)threadIdx.x;
   uint32_t ci = 0, cj = 0;  // bases consumed before this chunk
@@ -83,7 +117,9 @@ __global__ __launch_bounds__(64) void nwt_pileup_kernel(PileArgs q) {
     const uint32_t i0 = ci + si - di, j0 = cj + sj - dj;
     ci += (uint32_t)__shfl((int)si, 63, 64);
     cj += (uint32_t)__shfl((int)sj, 63, 64);
-    const bool ok = n > 0 && i0 + di <= pr.la && j0 + dj <= pr.lb;
+    // (an unknown operation matches no branch of the counts; the weights' last branch would take it)
+    const bool ok = n > 0 && i0 + di <= la && j0 + dj <= pr.lb && (!WEIGHTED || both || op == MC_CIGAR_I || op == MC_CIGAR_D);
+    // the counts: per run, or per column (percol) by the run's lane when it is short
     const bool percol = ok && (op == MC_CIGAR_X || (NAIVE && (op == MC_CIGAR_EQ || op == MC_CIGAR_D)));
     if (ok && !percol) {
       if (op == MC_CIGAR_EQ) {
@@ -103,99 +139,7 @@ __global__ __launch_bounds__(64) void nwt_pileup_kernel(PileArgs q) {
         atomicAdd(&tab[(uint64_t)(j0 + t) * MC_PILEUP_CH + ch], 1u);
       }
     }
-    unsigned long long wide = __ballot(percol && n > SPREAD);
-    while (wide) {  // (wave-uniform: one turn per long run of this chunk)
-      const int s = __ffsll(wide) - 1;
-      wide &= wide - 1;
-      const uint32_t bi = (uint32_t)__shfl((int)i0, s, 64), bj = (uint32_t)__shfl((int)j0, s, 64);
-      const uint32_t bn = (uint32_t)__shfl((int)n, s, 64), bop = (uint32_t)__shfl((int)op, s, 64);
-      for (uint32_t t = (uint32_t)lane; t < bn; t += 64) {
-        const uint32_t ch = bop == MC_CIGAR_D ? 5u : base_channel(a[bi + t]);
-        atomicAdd(&tab[(uint64_t)(bj + t) * MC_PILEUP_CH + ch], 1u);
-      }
-    }
-  }
-}
-
-// ---- the pile-up with quality weights (mc_nw_qpileup_strands) -------------------
-// nwt_qpileup_kernel: nwt_pileup_kernel's counts (the same difference arrays, per-column atomics
-// and finish kernel) and, beside them, a second table of the same shape that receives the read's
-// Phred values.  Qs(i), the quality of base i of seq1 as aligned, is qual[qoff + i] of a plus pair
-// and qual[qoff + la - 1 - i] of a minus pair: an index, the qualities are never reversed in memory.
-//   '=' / 'X' at (i, j)   wtable[j + t][channel of a[i + t]] += Qs(i + t) for every column of the run
-//   'D' of n at (i, j)    channel 5 of rows j .. j + n - 1 += min(Qs(i - 1) if i > 0, Qs(i) if i < la)
-//   'I' of n at (i, j)    channel 6 of row j += min Qs(i .. i + n - 1)
-// Every column carries its own value, so no difference array serves: a lane walks a run of at most
-// SPREAD columns itself, longer runs are taken one after the other by the whole wave, 64 columns
-// (consecutive quality bytes, consecutive rows) per step; a long 'I' run's minimum is a wave
-// minimum.  A zero weight issues no atomic.  Trip counts, bounds and the failed-traceback rule are
-// nwt_pileup_kernel's.
-struct QPileArgs {
-  PileArgs p;
-  const uint8_t *qual;   // the loaded qualities, at the sequences' offsets
-  const uint64_t *qoff;  // per pair: the offset of its read (as loaded, whatever the strand)
-  uint32_t *wtable;
-};
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d, 64));
-  return v;
-}
-
-__global__ __launch_bounds__(64) void nwt_qpileup_kernel(QPileArgs qa) {
-  const PileArgs &q = qa.p;
-  const uint32_t p = blockIdx.x;
-  if (p >= q.npairs) return;
-  const TracePair pr = q.pairs[p];
-  const uint32_t nw = (uint32_t)q.res[(uint64_t)p * TRACE_RES + 3], cap = pr.la + pr.lb;
-  if (nw == 0 || nw > cap) return;
-  const uint8_t *a = (pr.a_rc ? q.rc : q.codes) + pr.a_off;
-  const uint8_t *ql = qa.qual + qa.qoff[p];
-  const uint32_t la = pr.la;
-  const bool rc = pr.a_rc != 0;
-  auto Qs = [&](uint32_t i) -> uint32_t { return ql[rc ? la - 1 - i : i]; };  // i < la
-  auto gapq = [&](uint32_t i) -> uint32_t {  // the weight of a 'D' run with i read bases before it
-    uint32_t v = 0xffffffffu;
-    if (i > 0) v = Qs(i - 1);
-    if (i < la) v = min(v, Qs(i));
-    return v == 0xffffffffu ? 0u : v;
-  };
-  const uint32_t *src = q.ops + pr.ops_off + (cap - nw);
-  const uint64_t row0 = q.rowbase[p];
-  uint32_t *tab = q.table + row0 * MC_PILEUP_CH, *wt = qa.wtable + row0 * MC_PILEUP_CH;
-  int32_t *deq = q.deq + row0, *ddel = q.ddel + row0;
-  const int lane = (int)threadIdx.x;
-  uint32_t ci = 0, cj = 0;  // bases consumed before this chunk
-  const uint32_t nchunk = (nw + 63) / 64;
-  for (uint32_t c = 0; c < nchunk; c++) {
-    const uint32_t k = c * 64 + (uint32_t)lane;
-    const uint32_t w = k < nw ? src[k] : 0u;
-    const uint32_t n = w >> 4, op = w & 15u;
-    const bool both = op == MC_CIGAR_EQ || op == MC_CIGAR_X;
-    const uint32_t di = both || op == MC_CIGAR_I ? n : 0u, dj = both || op == MC_CIGAR_D ? n : 0u;
-    const uint32_t si = wave_scan(di, lane), sj = wave_scan(dj, lane);
-    const uint32_t i0 = ci + si - di, j0 = cj + sj - dj;
-    ci += (uint32_t)__shfl((int)si, 63, 64);
-    cj += (uint32_t)__shfl((int)sj, 63, 64);
-    const bool ok = n > 0 && i0 + di <= la && j0 + dj <= pr.lb && (both || op == MC_CIGAR_I || op == MC_CIGAR_D);
-    // the counts, as nwt_pileup_kernel<false>
-    if (ok) {
-      if (op == MC_CIGAR_EQ) {
-        atomicAdd(&deq[j0], 1);
-        atomicAdd(&deq[j0 + n], -1);
-      } else if (op == MC_CIGAR_D) {
-        atomicAdd(&ddel[j0], 1);
-        atomicAdd(&ddel[j0 + n], -1);
-      } else if (op == MC_CIGAR_I) {
-        atomicAdd(&tab[(uint64_t)j0 * MC_PILEUP_CH + 6], 1u);
-        atomicAdd(&tab[(uint64_t)j0 * MC_PILEUP_CH + 7], n);
-      }
-    }
-    if (ok && op == MC_CIGAR_X && n <= SPREAD)
-      for (uint32_t t = 0; t < n; t++) atomicAdd(&tab[(uint64_t)(j0 + t) * MC_PILEUP_CH + base_channel(a[i0 + t])], 1u);
-    // the weights of the short runs, by their lane
-    if (ok && n <= SPREAD) {
+    if (WEIGHTED && ok && n <= SPREAD) {  // the weights of the short runs, by their lane
       if (both) {
         for (uint32_t t = 0; t < n; t++) {
           const uint32_t v = Qs(i0 + t);
@@ -211,14 +155,19 @@ __global__ __launch_bounds__(64) void nwt_qpileup_kernel(QPileArgs qa) {
         if (v) atomicAdd(&wt[(uint64_t)j0 * MC_PILEUP_CH + 6], v);
       }
     }
-    // the long runs, one after the other by the whole wave: 'X' counts and every weight
-    unsigned long long wide = __ballot(ok && n > SPREAD);
+    // the long runs, one after the other by the whole wave: the per-column counts and every weight
+    unsigned long long wide = __ballot((WEIGHTED ? ok : percol) && n > SPREAD);
     while (wide) {  // (wave-uniform: one turn per long run of this chunk)
       const int s = __ffsll(wide) - 1;
       wide &= wide - 1;
       const uint32_t bi = (uint32_t)__shfl((int)i0, s, 64), bj = (uint32_t)__shfl((int)j0, s, 64);
       const uint32_t bn = (uint32_t)__shfl((int)n, s, 64), bop = (uint32_t)__shfl((int)op, s, 64);
-      if (bop == MC_CIGAR_EQ || bop == MC_CIGAR_X) {
+      if constexpr (!WEIGHTED) {
+        for (uint32_t t = (uint32_t)lane; t < bn; t += 64) {
+          const uint32_t ch = bop == MC_CIGAR_D ? 5u : base_channel(a[bi + t]);
+          atomicAdd(&tab[(uint64_t)(bj + t) * MC_PILEUP_CH + ch], 1u);
+        }
+      } else if (bop == MC_CIGAR_EQ || bop == MC_CIGAR_X) {
         for (uint32_t t = (uint32_t)lane; t < bn; t += 64) {
           const uint32_t ch = base_channel(a[bi + t]), v = Qs(bi + t);
           if (bop == MC_CIGAR_X) atomicAdd(&tab[(uint64_t)(bj + t) * MC_PILEUP_CH + ch], 1u);
@@ -270,10 +219,10 @@ int launch_nw_pileup(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint
                      const int32_t *d_res, const uint64_t *d_rowbase, uint32_t *d_table, int32_t *d_deq, int32_t *d_ddel,
                      bool naive) {
   if (m == 0) return MC_OK;
-  PileArgs q{(const uint8_t *)c->codes.p, d_rc, d_pairs, d_res, d_ops, d_rowbase, d_table, d_deq, d_ddel, m};
+  PileArgs q{(const uint8_t *)c->codes.p, d_rc, d_pairs, d_res, d_ops, d_rowbase, d_table, d_deq, d_ddel, m, nullptr, nullptr, nullptr};
   timed_begin(c);
-  if (naive) nwt_pileup_kernel<true><<<m, 64, 0, c->stream>>>(q);
-  else nwt_pileup_kernel<false><<<m, 64, 0, c->stream>>>(q);
+  if (naive) nwt_pileup_kernel<true, false><<<m, 64, 0, c->stream>>>(q);
+  else nwt_pileup_kernel<false, false><<<m, 64, 0, c->stream>>>(q);
   MCG_CHECK(hipGetLastError());
   timed_end(c, F_NW_PU);
   return MC_OK;
@@ -283,10 +232,10 @@ int launch_nw_qpileup(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uin
                       const int32_t *d_res, const uint64_t *d_rowbase, const uint64_t *d_qoff, uint32_t *d_table,
                       uint32_t *d_wtable, int32_t *d_deq, int32_t *d_ddel) {
   if (m == 0) return MC_OK;
-  QPileArgs q{{(const uint8_t *)c->codes.p, d_rc, d_pairs, d_res, d_ops, d_rowbase, d_table, d_deq, d_ddel, m},
-              (const uint8_t *)c->qual.p, d_qoff, d_wtable};
+  PileArgs q{(const uint8_t *)c->codes.p, d_rc, d_pairs, d_res, d_ops, d_rowbase, d_table, d_deq, d_ddel, m,
+             (const uint8_t *)c->qual.p, d_qoff, d_wtable};
   timed_begin(c);
-  nwt_qpileup_kernel<<<m, 64, 0, c->stream>>>(q);
+  nwt_pileup_kernel<false, true><<<m, 64, 0, c->stream>>>(q);
   MCG_CHECK(hipGetLastError());
   timed_end(c, F_NW_PU);
   return MC_OK;

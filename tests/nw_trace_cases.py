@@ -49,6 +49,40 @@ def choice_bytes(la, lb):
     return (la + 64 * r - 1) // (64 * r) * (lb + 63) * 32 * r
 
 
+def batch_ends(lens, a, b, am, pairs, nbytes, scratch=0):
+    """The batches of host/pairbatch.hpp restated -> one (i1, why) per batch: where it ends and which
+    cap ended it ("pairs", "scratch", "bytes"; "end": the list did).  lens: the points' lengths;
+    am: a strand flag per pair (None: all plus); scratch 0: no scratch rule (the identities)."""
+    out, i0, m = [], 0, len(a)
+    while i0 < m:
+        i1, uniq, pad, scr, why = i0, set(), 0, 0, "end"
+        while i1 < m and why == "end":
+            la, lb = lens[a[i1]], lens[b[i1]] if b is not None else 0
+            need, string = choice_bytes(la, lb) if scratch else 0, (la + 15) // 16 * 16
+            new = am is not None and bool(am[i1]) and int(a[i1]) not in uniq
+            if i1 - i0 >= pairs:
+                why = "pairs"
+            elif scratch and i1 > i0 and scr + need > scratch:
+                why = "scratch"
+            elif new and uniq and pad + string > nbytes:
+                why = "bytes"
+            else:
+                if new:
+                    pad += string
+                    uniq.add(int(a[i1]))
+                scr += need
+                i1 += 1
+        out.append((i1, why))
+        i0 = i1
+    return out
+
+
+def ident_bytes(lens, a):
+    """A value of MC_IDENT_BYTES that puts batch ends inside a list of minus reads a: three times
+    the longest one's padded string."""
+    return 3 * ((max(lens[i] for i in a) + 15) // 16 * 16)
+
+
 class Cases:
     """codes: the points (both halves); pairs: name -> (a, b) ids of the first half."""
 

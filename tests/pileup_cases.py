@@ -9,7 +9,8 @@ channel 7.
 
 The pairs: the whole list of nw_trace_cases (whose expectations test_nw_trace_host.py ties to the
 CPU oracle), then what only a pile-up can get wrong: 150 reads on one centre, a pair of more than
-64 runs, a planted-truth family whose consensus is known, and a target no pair names.  Points are
+64 runs, a planted-truth family whose consensus is known, a target no pair names, and a pair with
+a run of more than 64 'X'.  Points are
 nw_trace_cases' (both halves) followed by the new ones; a minus pair's expectation is the
 alignment of the read's minus-strand string."""
 import numpy as np
@@ -166,6 +167,16 @@ class Pile:
             b.append(self.planted)
             names.append("p%02d" % k)
         self.lonely = point(rng.integers(0, 4, 33).astype(np.uint8))  # a target with no pair
+        # the one class of runs no pair above has (test_pileup_host.py's census): more than 64 'X'.
+        # 70 bases of one letter in a 260-base centre, of another in the read: 95=70X95= on the
+        # plus strand, and a run of 71 on the minus strand (the complement differs from it too)
+        xc = np.random.default_rng(260).integers(0, 4, 260).astype(np.uint8)
+        xc[95:165] = 0
+        xr = xc.copy()
+        xr[95:165] = 2
+        a.append(point(xr))
+        b.append(point(xc))
+        names.append("x70")
         self.a, self.b, self.names = np.array(a, np.uint32), np.array(b, np.uint32), names
         seen, targets = set(), []
         for j in list(self.b) + [self.lonely]:

@@ -23,6 +23,7 @@ import pytest
 
 import fixtures
 import meshclust_amd as M
+import nw_trace_cases as T
 
 pytestmark = pytest.mark.gpu
 
@@ -131,7 +132,8 @@ def rcpoint(ids):
 
 
 # ---------------------------------------------------------------- 1. the strings
-def test_revcomp_sequences_equal_numpy(eng, points):
+def test_revcomp_sequences_equal_numpy(eng, points, monkeypatch):
+    monkeypatch.delenv("MC_IDENT_BYTES", raising=False)
     codes, _ = points
     seq_off = load(eng, points)
     for j, n in enumerate(LENS):  # every length at every alignment of its source bytes
@@ -155,6 +157,14 @@ def test_revcomp_sequences_equal_numpy(eng, points):
     assert (g[45:51] == ord("N")).all() and (g[:45] <= 3).all() and (g[51:] <= 3).all()
     got0, off0 = eng.revcomp_sequences([])
     assert len(got0) == 0 and list(off0) == [0]
+    # batches that end by the cap on the strings' bytes (host/pairbatch.hpp's rule restated): the same bytes
+    lens = [len(x) for x in codes]
+    nbytes = T.ident_bytes(lens, ids)
+    ends = T.batch_ends(lens, ids, None, np.ones(len(ids), np.uint8), 1 << 20, nbytes)
+    assert sum(1 for _, why in ends if why == "bytes") >= 2 and ends[-1][0] - ends[-2][0] >= 4  # (the repeated ids in one batch)
+    monkeypatch.setenv("MC_IDENT_BYTES", str(nbytes))
+    got2, off2 = eng.revcomp_sequences(ids)
+    assert np.array_equal(got2, got) and np.array_equal(off2, off)
 
 
 # ---------------------------------------------------------------- 2. no minus pair
@@ -201,6 +211,7 @@ def same(x, y):
 @pytest.mark.parametrize("batch", [None, "7"], ids=["one_batch", "batch7"])
 def test_no_minus_pair_is_nw_identity(eng, points, lists, batch, monkeypatch):
     load(eng, points)
+    monkeypatch.delenv("MC_IDENT_BYTES", raising=False)
     if batch:
         monkeypatch.setenv("MC_IDENT_BATCH", batch)
     else:
@@ -213,14 +224,21 @@ def test_no_minus_pair_is_nw_identity(eng, points, lists, batch, monkeypatch):
 
 
 # ---------------------------------------------------------------- 3. minus and mixed batches
-@pytest.mark.parametrize("batch", [None, "7"], ids=["one_batch", "batch7"])
+@pytest.mark.parametrize("batch", [None, "7", "bytes"], ids=["one_batch", "batch7", "bytes"])
 def test_minus_pairs_align_the_reverse_complemented_read(eng, points, lists, batch, monkeypatch):
     load(eng, points)
-    if batch:
-        monkeypatch.setenv("MC_IDENT_BATCH", batch)
-    else:
-        monkeypatch.delenv("MC_IDENT_BATCH", raising=False)
+    for var in ("MC_IDENT_BATCH", "MC_IDENT_BYTES"):
+        monkeypatch.delenv(var, raising=False)
     pl, ref = lists
+    if batch == "bytes":  # batches that end by the cap on the strings' bytes (host/pairbatch.hpp's rule restated)
+        lens = [len(x) for x in points[0]]
+        nbytes = T.ident_bytes(lens, np.concatenate([a[am != 0] for a, _, am in pl.values()]))
+        for name in ("m65", "m1100_mixed", "m1100_minus"):
+            a, b, am = pl[name]
+            assert sum(1 for _, why in T.batch_ends(lens, a, b, am, 1 << 20, nbytes) if why == "bytes") >= 2, name
+        monkeypatch.setenv("MC_IDENT_BYTES", str(nbytes))
+    elif batch:
+        monkeypatch.setenv("MC_IDENT_BATCH", batch)
     assert set(pl) == {"m1", "m65", "m1100_mixed", "m1100_minus", "big", "repeat"}
     for name, (a, b, am) in pl.items():
         want, plus = ref[name]
@@ -313,7 +331,7 @@ class E2E:
             tsv, hits, stats, rest = (self.tmp / (name + ext) for ext in (".tsv", ".hits", ".json", ".rest.fa"))
             args = (["--top", "3", "--hits", str(hits)] if top else []) + ["--stats-json", str(stats), "--unassigned", str(rest)]
             e = dict(os.environ, **(env or {}))
-            for var in ("MC_ASSIGN_FORM", "MC_ASSIGN_TILE", "MC_ASSIGN_PAIRS", "MC_IDENT_BATCH"):
+            for var in ("MC_ASSIGN_FORM", "MC_ASSIGN_TILE", "MC_ASSIGN_PAIRS", "MC_IDENT_BATCH", "MC_IDENT_BYTES"):
                 if not env or var not in env:
                     e.pop(var, None)
             r = subprocess.run([ASSIGN_BIN, "--model", str(self.model), "--centres", str(self.cen), str(reads), "--output",

@@ -40,7 +40,7 @@ def mixed():
 
 
 def clean_env(monkeypatch, **kw):
-    for var in ("MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH", "MC_IDENT_BATCH"):
+    for var in ("MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH", "MC_IDENT_BATCH", "MC_IDENT_BYTES"):
         monkeypatch.delenv(var, raising=False)
     for k, v in kw.items():
         monkeypatch.setenv(k, str(v))
@@ -49,7 +49,7 @@ def clean_env(monkeypatch, **kw):
 @pytest.fixture(scope="module")
 def got(eng):
     """The device's answers with the default caps, computed once: plus, minus."""
-    for var in ("MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH", "MC_IDENT_BATCH"):
+    for var in ("MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH", "MC_IDENT_BATCH", "MC_IDENT_BYTES"):
         assert var not in os.environ
     c = T.cases()
     return (eng.nw_align_strands(c.a, c.b, None), eng.nw_align_strands(c.a, c.b, np.ones(len(c.a), np.uint8)))
@@ -108,8 +108,13 @@ def test_batches_give_the_same_bytes(eng, mixed, monkeypatch):
     big = T.choice_bytes(1100, 1100)
     n_big = sum(1 for i in c.a if len(c.codes[i]) > 1024)
     assert n_big >= 6 and big == max(T.choice_bytes(len(c.codes[i]), len(c.codes[j])) for i, j in zip(c.a, c.b))
+    # MC_IDENT_BYTES: batch ends by the cap on the minus-strand strings (host/pairbatch.hpp's rule restated)
+    lens = [len(x) for x in c.codes]
+    nbytes = T.ident_bytes(lens, c.a[am != 0])
+    by = [i1 for i1, why in T.batch_ends(lens, c.a, c.b, am, 1 << 16, nbytes, 1 << 30) if why == "bytes"]
+    assert len(by) >= 2, (nbytes, by)
     for env in ({"MC_ALIGN_BATCH": 7}, {"MC_ALIGN_SCRATCH": 3 * big + 64}, {"MC_ALIGN_BATCH": 7, "MC_ALIGN_SCRATCH": 3 * big + 64},
-                {"MC_ALIGN_BATCH": 1}):
+                {"MC_ALIGN_BATCH": 1}, {"MC_IDENT_BYTES": nbytes}, {"MC_ALIGN_BATCH": 7, "MC_IDENT_BYTES": nbytes}):
         clean_env(monkeypatch, **env)
         res = eng.nw_align_strands(c.a, c.b, am)
         assert all(x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(res, base)), env
@@ -219,7 +224,7 @@ def e2e(built, tmp_path_factory):
         for i, (h, s) in enumerate(recs):
             f.write(h + b"\n" + (s.upper().translate(_RC)[::-1] if i % 2 else s) + b"\n")
     env = {k: v for k, v in os.environ.items() if k not in ("MC_ASSIGN_FORM", "MC_ASSIGN_TILE", "MC_ASSIGN_PAIRS", "MC_IDENT_BATCH",
-                                                             "MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH")}
+                                                             "MC_IDENT_BYTES", "MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH")}
     done = {}
 
     def run(name, extra):

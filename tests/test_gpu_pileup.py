@@ -19,7 +19,7 @@ import pileup_cases as P
 pytestmark = pytest.mark.gpu
 
 ASSIGN_BIN = os.path.join(os.path.dirname(M.BIN), "meshclust-assign")
-ENV_VARS = ("MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH", "MC_IDENT_BATCH", "MC_PILEUP_NAIVE")
+ENV_VARS = ("MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH", "MC_IDENT_BATCH", "MC_IDENT_BYTES", "MC_PILEUP_NAIVE")
 
 
 @pytest.fixture(scope="module")
@@ -75,8 +75,14 @@ def test_batches_give_the_same_bytes(eng, monkeypatch):
     assert np.array_equal(base[0], P.expected_table(am))
     big = T.choice_bytes(1100, 1100)
     assert big == max(T.choice_bytes(len(p.codes[i]), len(p.codes[j])) for i, j in zip(p.a, p.b))
+    # MC_IDENT_BYTES: the batch end no other cap reaches, several times in the list and inside the
+    # contended centre's reads (host/pairbatch.hpp's rule restated: nw_trace_cases.batch_ends)
+    lens = [len(x) for x in p.codes]
+    nbytes = T.ident_bytes(lens, p.a[am != 0])
+    by = [i1 for i1, why in T.batch_ends(lens, p.a, p.b, am, 1 << 16, nbytes, 1 << 30) if why == "bytes"]
+    assert len(by) >= 2 and any(p.b[i1 - 1] == p.contended == p.b[i1] for i1 in by), (nbytes, by)
     for env in ({"MC_ALIGN_BATCH": 7}, {"MC_ALIGN_BATCH": 1}, {"MC_ALIGN_SCRATCH": 3 * big + 64}, {"MC_PILEUP_NAIVE": 1},
-                {"MC_PILEUP_NAIVE": 1, "MC_ALIGN_BATCH": 7}):
+                {"MC_PILEUP_NAIVE": 1, "MC_ALIGN_BATCH": 7}, {"MC_IDENT_BYTES": nbytes}):
         clean_env(monkeypatch, **env)
         res = eng.nw_pileup_strands(p.a, p.b, am, p.targets)
         assert all(x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(res, base)), env

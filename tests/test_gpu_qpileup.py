@@ -22,7 +22,7 @@ import qpileup_cases as Q
 pytestmark = pytest.mark.gpu
 
 ASSIGN_BIN = os.path.join(os.path.dirname(M.BIN), "meshclust-assign")
-ENV_VARS = ("MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH", "MC_IDENT_BATCH", "MC_PILEUP_NAIVE")
+ENV_VARS = ("MC_ALIGN_BATCH", "MC_ALIGN_SCRATCH", "MC_IDENT_BATCH", "MC_IDENT_BYTES", "MC_PILEUP_NAIVE")
 
 
 @pytest.fixture(scope="module")
@@ -75,7 +75,12 @@ def test_batches_give_the_same_bytes(eng, monkeypatch):
     base = eng.nw_qpileup_strands(p.a, p.b, am, p.targets)
     assert np.array_equal(base[1], Q.expected_wtable(am))
     big = T.choice_bytes(1100, 1100)
-    for env in ({"MC_ALIGN_BATCH": 7}, {"MC_ALIGN_BATCH": 1}, {"MC_ALIGN_SCRATCH": 3 * big + 64}):
+    # MC_IDENT_BYTES: as test_gpu_pileup.py, batch ends by the byte cap, one of them inside the contended centre's reads
+    lens = [len(x) for x in p.codes]
+    nbytes = T.ident_bytes(lens, p.a[am != 0])
+    by = [i1 for i1, why in T.batch_ends(lens, p.a, p.b, am, 1 << 16, nbytes, 1 << 30) if why == "bytes"]
+    assert len(by) >= 2 and any(p.b[i1 - 1] == p.contended == p.b[i1] for i1 in by), (nbytes, by)
+    for env in ({"MC_ALIGN_BATCH": 7}, {"MC_ALIGN_BATCH": 1}, {"MC_ALIGN_SCRATCH": 3 * big + 64}, {"MC_IDENT_BYTES": nbytes}):
         clean_env(monkeypatch, **env)
         assert same(eng.nw_qpileup_strands(p.a, p.b, am, p.targets), base), env
     # a second call overwrites: fewer pairs give smaller tables

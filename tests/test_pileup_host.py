@@ -40,7 +40,8 @@ def target_view(am):
 def test_the_list_holds_the_new_cases(built):
     p = P.pile()
     plus, minus = P.expected()
-    assert len(p.a) == p.nbase + 150 + 1 + 30 and list(p.a[:p.nbase]) == list(p.base.a)
+    assert len(p.a) == p.nbase + 150 + 1 + 30 + 1 and list(p.a[:p.nbase]) == list(p.base.a)
+    assert p.names[-1] == "x70" and T.cigar_string(plus[-1][0]) == "95=70X95="
     assert sum(1 for j in p.b if j == p.contended) == 150 and sum(1 for j in p.b if j == p.planted) == 30
     assert p.lonely in p.targets and p.lonely not in p.b and len(set(p.targets.tolist())) == len(p.targets)
     wide = p.base.pairs["b1100x1100"][1]
@@ -53,6 +54,34 @@ def test_the_list_holds_the_new_cases(built):
         for k in range(p.nbase, len(p.a)):
             _, o_len, o_ids, o_score = O.nw(p.read(k, bool(s)).tobytes(), p.codes[p.b[k]].tobytes())
             assert res[k][1:] == (o_score, o_len, o_ids), (p.names[k], s)
+
+
+def test_every_class_of_runs_the_kernels_branch_on(built):
+    """The pile-up kernels (gpu/pileup.hip) treat a run by its operation and its length: at most
+    SPREAD = 8 columns by its own lane, more by the whole wave 64 columns at a time, so a run of
+    more than 64 takes a second turn of that loop.  The runs of the list per class, <= 8 / 9 .. 64 /
+    > 64, with the strands test_gpu_pileup.py and test_gpu_qpileup.py use:
+
+               X                  I                 D                 =
+      plus     7882 /  1 / 1      959 / 40 /  4     1165 / 45 / 2     8138 / 1619 / 66
+      minus   17738 /  9 / 1     2644 / 90 / 18     2827 / 58 / 1    20943 /    6 /  0
+      mixed   14273 /  5 / 1     2043 / 74 / 13     2258 / 51 / 1    16440 /  572 / 18
+
+    Without the pair "x70" no strand has an 'X' run of more than 64.  Every class of X, I and D is
+    asserted for every strand choice; '=' (which only the weighted and the naive kernel walk by
+    column) for the plus and the mixed one: the list has no read that is related to its centre on
+    the minus strand."""
+    p = P.pile()
+    exp = P.expected()
+    for name, am in (("plus", np.zeros(len(p.a), np.uint8)), ("minus", np.ones(len(p.a), np.uint8)), ("mixed", P.mixed_strands())):
+        cnt = {}
+        for k in range(len(p.a)):
+            for w in exp[am[k]][k][0]:
+                n, op = int(w) >> 4, int(w) & 15
+                key = (T.OPCH[op], 0 if n <= 8 else 1 if n <= 64 else 2)
+                cnt[key] = cnt.get(key, 0) + 1
+        for op in "XID" + ("=" if name != "minus" else ""):
+            assert all(cnt.get((op, c), 0) > 0 for c in range(3)), (name, op, cnt)
 
 
 @pytest.mark.parametrize("strands", ["plus", "minus", "mixed"])
