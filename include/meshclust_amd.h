@@ -479,6 +479,69 @@ int mc_nw_qpileup_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, con
                           int32_t *score, int32_t *len, int32_t *ids /* m each, may be NULL */);
 
 /*
+ * THE ALIGNMENTS of mc_nw_align_strands laid out in common columns per centre: a centre-anchored
+ * multiple alignment, the pile-up's sibling that keeps the inserted bases.  Pairs, operand rule,
+ * strands, batching and caps are mc_nw_align_strands' own: seq1 is the read a[i], or its minus-strand
+ * string where a_minus[i] != 0; seq2 is the centre b[i] as written.  targets are nt distinct centre
+ * ids, as for mc_nw_pileup_strands; target t of L bytes owns rows row_off[t] .. row_off[t + 1],
+ * L + 1 of them.  For target t with centre bytes c[0 .. L) and its pairs (those with b[i] == targets[t]):
+ *   ins(i, r)   the length of pair i's 'I' run met with r centre bases consumed, 0 if there is none
+ *               (a pair has at most one 'I' run per r)
+ *   w[r]        max over the pairs of ins(i, r), r = 0 .. L; 0 for a target without pairs
+ *   col[r]      r + w[0] + .. + w[r] for r < L: the column of centre base r; its w[r] insertion
+ *               slots are the columns col[r] - w[r] .. col[r] - 1
+ *   W           L + w[0] + .. + w[L], the block's width; col[L] = W, the trailing slots are
+ *               W - w[L] .. W - 1
+ * The character of a byte x is "ACGT"[x] for x <= 3, else the byte itself (the FASTA writer's
+ * rule); the gap is MC_MSA_GAP.
+ *   centre row  the centre's characters at col[r], gaps elsewhere
+ *   pair row    walking the alignment with i read bases and j centre bases consumed: '=' / 'X' writes
+ *               the character of seq1[i] at col[j]; 'D' leaves a gap at col[j]; an 'I' run of n writes
+ *               the characters of seq1[i .. i + n) at col[j] - w[j] + t for t < n (left-justified, the
+ *               remaining w[j] - n slots are gaps); every slot where the pair has no 'I' run is a gap
+ * Every row of a block has exactly W bytes.  Removing the gaps from a pair row gives seq1 as aligned,
+ * from the centre row the centre; every column holds a non-gap in at least one row of the block.
+ * The bytes depend neither on the order of the pairs nor on any batching.
+ *
+ * mc_nw_msa_begin aligns every pair once (mc_nw_align_strands' forward and traceback kernels, its
+ * batches and environment caps) and leaves a plan with the context: w and col of every row and
+ * every pair's packed operation words, in device buffers the plan owns (no other entry touches them;
+ * other alignment entries may be called between begin and rows), the pair list on the host.
+ * row_off (nt + 1, required) receives the prefix sums of L + 1, width (row_off[nt], may be NULL)
+ * every w[r], block_width (nt, required) every W; score / len / ids (m each, may be NULL) are
+ * mc_nw_align_strands' bit for bit.  Errors are mc_nw_pileup_strands': a duplicate target, an id >= n
+ * or a b[i] that is no target is MC_ERR_ARG, a pair above the scratch cap MC_ERR_UNSUPPORTED, both
+ * found before any launch, nothing written, row_off included; no sequences: MC_ERR_STATE.  A
+ * W >= 2^31 is MC_ERR_UNSUPPORTED and leaves no plan.  m = 0 is MC_OK: every block is its centre
+ * alone (W = L).  A begin drops the plan before it whether it succeeds or not; mc_nw_msa_end (which
+ * also frees the plan's device buffers), mc_load_sequences, mc_load_packed and mc_ctx_destroy drop it too.
+ *
+ * mc_nw_msa_rows renders rows first .. first + count: row k < nt is target k's centre row, row
+ * nt + i pair i's.  off (count + 1, required) receives the prefix sums of the rows' lengths, each
+ * the W of the row's target.  out == NULL: the offsets only, no device work.  out != NULL with
+ * cap < off[count]: MC_ERR_ARG, off valid, nothing written to out.  A range past nt + m:
+ * MC_ERR_ARG.  No plan: MC_ERR_STATE.  count = 0: MC_OK.  The rows are rendered in batches: a batch
+ * ends before the row that would take its output past MC_MSA_BATCH_BYTES (a longer row gets a batch
+ * of its own) and where MC_IDENT_BYTES ends a batch of minus-strand strings (the distinct minus
+ * reads of a batch are reverse-complemented once).  Environment, read per call: MC_MSA_BYTES=<bytes>
+ * lowers the first cap.  Batching, and the split of the rows over calls, change no byte.
+ * Device: a wavefront per pair max-es its 'I' runs into w (integer atomics), a wavefront per target
+ * scans w into col and W, a wavefront per row renders it, every byte stored exactly once.  All are
+ * timed as "nw", the reverse complement as "layout".  mc_nw_msa_profile: out[0 .. 3] = device ms of
+ * the forward, the traceback (+ packing), the width + column and the render kernels since the last
+ * reset (a reset also clears mc_nw_align_profile's two times).
+ */
+#define MC_MSA_GAP '-'
+#define MC_MSA_BATCH_BYTES (256ull << 20)
+int mc_nw_msa_begin(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                    const uint32_t *targets, uint32_t nt, uint64_t *row_off /* nt + 1, required */,
+                    uint32_t *width /* row_off[nt], may be NULL */, uint64_t *block_width /* nt, required: W per target */,
+                    int32_t *score, int32_t *len, int32_t *ids /* m each, may be NULL */);
+int mc_nw_msa_rows(mc_ctx *ctx, uint64_t first, uint64_t count, uint8_t *out, uint64_t cap, uint64_t *off /* count + 1, required */);
+int mc_nw_msa_end(mc_ctx *ctx);
+int mc_nw_msa_profile(mc_ctx *ctx, double *out /* 4 */, int reset);
+
+/*
  * Accumulation (ClusterFactory::accumulate, ClusterFactory.cpp:637-714).
  * The bvec of Runner.cpp:342-350 is only ever shrunk after insert_finalize, so the device
  * holds one static candidate order (bin-major, length-sorted within bins) plus an alive

@@ -34,6 +34,7 @@ ERR_ARG, ERR_UNSUPPORTED = 1, 6
 ERR_STATE = 3
 CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # MC_CIGAR_*: mc_nw_align_strands' words are run << 4 | op
 PILEUP_CH = 8  # MC_PILEUP_CH: counters per row of mc_nw_pileup_strands' table
+MSA_GAP = ord("-")  # MC_MSA_GAP: the gap byte of mc_nw_msa_rows
 QUAL_MAX = 93  # MC_QUAL_MAX: the largest Phred value mc_load_qualities takes
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
@@ -131,6 +132,13 @@ def gpu_lib():
         lib.mc_nw_qpileup_strands.restype = C.c_int
         lib.mc_nw_qpileup_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("mc_nw_msa_begin", "mc_nw_msa_rows", "mc_nw_msa_end", "mc_nw_msa_profile"):
+            getattr(lib, name).restype = C.c_int
+        lib.mc_nw_msa_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mc_nw_msa_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.mc_nw_msa_end.argtypes = [C.c_void_p]
+        lib.mc_nw_msa_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _bind_steps(lib)
         _gpu = lib
     return _gpu
@@ -216,6 +224,10 @@ def host_lib():
         lib.mcl_assign_qconsensus.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                               C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
                                               C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
+        lib.mcl_assign_msa.restype = C.c_int
+        lib.mcl_assign_msa.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                       C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
+                                       C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -679,6 +691,53 @@ class Engine:
         self._ck(self.lib.mc_nw_pileup_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_pileup_profile")
         return float(out[0]), float(out[1]), float(out[2])
 
+    def nw_msa_begin(self, a, b, a_minus, targets):
+        """mc_nw_msa_begin: nw_align_strands' alignments laid out in common columns per centre ->
+        (row_off, width, block_width, score, len, ids).  ``targets``: the distinct centres (every b
+        among them); target t of L bytes owns rows row_off[t] .. row_off[t + 1] (L + 1 of them);
+        ``width[r]`` is the longest insertion any of its pairs has before centre base r (row L: after the
+        last), ``block_width[t]`` = L + the sum of its widths, the length of every row of its block.
+        The plan stays with the engine until the next begin, nw_msa_end or a load of sequences."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        am = None if a_minus is None else np.ascontiguousarray(a_minus, np.uint8)
+        tg = np.ascontiguousarray(targets, np.uint32)
+        assert len(b) == len(a) and (am is None or len(am) == len(a))
+        m, nt = len(a), len(tg)
+        off = np.zeros(nt + 1, np.uint64)
+        self._ck(self.lib.mc_revcomp_sequences(self.ctx, _p(tg), C.c_uint64(nt), None, _p(off)), "mc_revcomp_sequences")
+        width = np.zeros(int(off[-1]) + nt, np.uint32)  # (the targets' lengths, no device work: L + 1 rows each)
+        bw = np.zeros(nt, np.uint64)
+        sc = np.zeros(m, np.int32)
+        ln = np.zeros(m, np.int32)
+        ids = np.zeros(m, np.int32)
+        self._ck(self.lib.mc_nw_msa_begin(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(m), _p(tg), C.c_uint32(nt), _p(off), _p(width),
+                                        _p(bw), _p(sc), _p(ln), _p(ids)), "mc_nw_msa_begin")
+        return off, width, bw, sc, ln, ids
+
+    def nw_msa_rows(self, first, count, rows=True):
+        """mc_nw_msa_rows: rows first .. first + count of the plan (row k < nt: target k's centre row;
+        row nt + i: pair i's) -> (bytes, off): row k's characters are bytes[off[k] .. off[k + 1]), gaps
+        MSA_GAP.  ``rows=False``: the offsets only (bytes is None, no device work)."""
+        off = np.zeros(count + 1, np.uint64)
+        self._ck(self.lib.mc_nw_msa_rows(self.ctx, C.c_uint64(first), C.c_uint64(count), None, C.c_uint64(0), _p(off)), "mc_nw_msa_rows")
+        if not rows:
+            return None, off
+        out = np.zeros(int(off[-1]), np.uint8)
+        self._ck(self.lib.mc_nw_msa_rows(self.ctx, C.c_uint64(first), C.c_uint64(count), _p(out), C.c_uint64(len(out)), _p(off)),
+                 "mc_nw_msa_rows")
+        return out, off
+
+    def nw_msa_end(self):
+        """mc_nw_msa_end: drop the plan and free its device buffers."""
+        self._ck(self.lib.mc_nw_msa_end(self.ctx), "mc_nw_msa_end")
+
+    def nw_msa_profile(self, reset=False):
+        """mc_nw_msa_profile -> (forward ms, traceback ms, width + column ms, render ms) since the last reset."""
+        out = np.zeros(4)
+        self._ck(self.lib.mc_nw_msa_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_msa_profile")
+        return tuple(float(x) for x in out)
+
     def nw_identity_raw(self, a_cat, a_off, b_cat, b_off):
         a_cat = np.ascontiguousarray(a_cat, np.uint8)
         b_cat = np.ascontiguousarray(b_cat, np.uint8)
@@ -704,7 +763,7 @@ class Engine:
 
 
 def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None,
-                 identity=False, min_identity=None, paf=None, consensus=None, pileup=None, quality=False):
+                 identity=False, min_identity=None, paf=None, consensus=None, pileup=None, quality=False, msa=None):
     """Place the reads of the FASTA or FASTQ file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
@@ -730,13 +789,23 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     ``realigned_centres`` and ``insertion_sites``.
     ``quality``: meshclust-assign's --quality (mcl_assign_qconsensus; with ``consensus`` and/or ``pileup``, every
     reads file FASTQ): the pile-up is weighed by base quality (mc_nw_qpileup_strands), ``consensus`` is written
-    as FASTQ with a quality per base, the ``pileup`` rows gain wA wC wG wT wN wdel, the stats ``quality``."""
+    as FASTQ with a quality per base, the ``pileup`` rows gain wA wC wG wT wN wdel, the stats ``quality``.
+    ``msa``: meshclust-assign's --msa FILE (mcl_assign_msa; implies ``identity``): the assigned reads of every centre
+    laid out in common columns (mc_nw_msa_begin / mc_nw_msa_rows) as aligned FASTA, a pass of its own that changes
+    no other output; the stats gain, last, ``msa_pairs``, ``msa_centres``, ``msa_columns``, ``msa_bytes`` and the
+    ``msa`` phase."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    if quality:
+    if msa is not None:
+        rc = lib.mcl_assign_msa(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
+                                hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),
+                                paf.encode() if paf else None, consensus.encode() if consensus else None,
+                                pileup.encode() if pileup else None, 1 if quality else 0, msa.encode(), buf, len(buf))
+    elif quality:
         rc = lib.mcl_assign_qconsensus(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                        unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
                                        hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),

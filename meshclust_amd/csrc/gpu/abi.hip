@@ -261,7 +261,7 @@ int mc_ctx_destroy(mc_ctx *c) {
                  &c->s_c, &c->s_d, &c->s_e, &c->s_f, &c->s_g, &c->s_h, &c->s_i, &c->s_j, &c->s_k, &c->hs, &c->mag_s, &c->sumsq_s, &c->len_s, &c->ticket,
                  &c->msum, &c->ident_s, &c->al_a, &c->al_b, &c->al_out, &c->al_id, &c->ord_ids, &c->acc_out, &c->sp_words, &c->sp_keys,
                  &c->sp_scr, &c->sp_nodes, &c->sp_nn, &c->sp_q, &c->sp_err, &c->u_off, &c->u_mem, &c->nw_items, &c->nw_gran, &c->rc_seq, &c->tr_choice, &c->tr_bnd, &c->tr_ops, &c->tr_pairs, &c->tr_res, &c->tr_idx, &c->tr_dst,
-                 &c->tr_out, &c->tr_err, &c->pu_table, &c->pu_diff, &c->pu_rows, &c->pu_toff, &c->pu_roff, &c->qual, &c->pu_wtable, &c->pu_qoff, &c->hist_fwd, &c->or_runs})
+                 &c->tr_out, &c->tr_err, &c->pu_table, &c->pu_diff, &c->pu_rows, &c->pu_toff, &c->pu_roff, &c->qual, &c->pu_wtable, &c->pu_qoff, &c->msa_width, &c->msa_col, &c->msa_words, &c->msa_bw, &c->msa_rec, &c->msa_out, &c->hist_fwd, &c->or_runs})
     release(*b);
   if (c->h_scan) (void)hipHostFree(c->h_scan);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -311,6 +311,7 @@ int mc_load_sequences(mc_ctx *c, const uint8_t *codes, const uint64_t *seq_off, 
     c->h_uoff.clear();
     c->h_umem.clear();
     c->has_qual = false;  // (mc_load_qualities' values belonged to the sequences replaced here)
+    msa_drop(c);          // (and mc_nw_msa_begin's plan)
   }
   if (!c || !seq_off || !seg_off || (n && !codes)) return MC_ERR_ARG;
   std::vector<uint64_t> pk_off;
@@ -329,6 +330,7 @@ int mc_load_packed(mc_ctx *c, const uint32_t *packed, const uint64_t *pk_off, co
     c->h_uoff.clear();
     c->h_umem.clear();
     c->has_qual = false;  // (mc_load_qualities' values belonged to the sequences replaced here)
+    msa_drop(c);          // (and mc_nw_msa_begin's plan)
   }
   if (!c || !pk_off || !seq_off || !seg_off || (n && !packed) || (nexc && (!exc_pos || !exc_val))) return MC_ERR_ARG;
   for (uint64_t i = 0; i < n; i++)

@@ -1,5 +1,6 @@
 // abi_align.hip -- the alignment entries of include/meshclust_amd.h on lists of pairs that may sit
-// on either strand: minus-strand strings, identities, alignments, pile-ups and their profiles.
+// on either strand: minus-strand strings, identities, alignments, pile-ups, multiple alignments and
+// their profiles.
 // Every list is cut into batches by host/pairbatch.hpp; as everywhere in libmcgpu the entries are
 // synchronous and fail loudly.
 #include <hip/hip_runtime.h>
@@ -116,6 +117,28 @@ int align_check_caps(mc_ctx *c, const char *who, const uint32_t *a, const uint32
   return MC_OK;
 }
 
+// tindex[point id] = its place among the targets (NO_TARGET: none); MC_ERR_ARG for a target listed
+// twice or a b[i] that is no target
+constexpr uint32_t NO_TARGET = 0xffffffffu;
+int index_targets(mc_ctx *c, const std::string &who, const uint32_t *targets, uint32_t nt, const uint32_t *b, uint64_t m,
+                  std::vector<uint32_t> &tindex) {
+  tindex.assign(c->n, NO_TARGET);
+  for (uint32_t t = 0; t < nt; t++) {
+    if (tindex[targets[t]] != NO_TARGET) {
+      set_error(who + ": point " + std::to_string(targets[t]) + " is listed twice among the targets");
+      return MC_ERR_ARG;
+    }
+    tindex[targets[t]] = t;
+  }
+  for (uint64_t i = 0; i < m; i++)
+    if (tindex[b[i]] == NO_TARGET) {
+      set_error(who + ": pair " + std::to_string(i) + "'s seq2, point " + std::to_string(b[i]) +
+                ", is not among the targets");
+      return MC_ERR_ARG;
+    }
+  return MC_OK;
+}
+
 // mc_nw_pileup_strands (weighted false, wtable NULL) and mc_nw_qpileup_strands (weighted: the
 // same call with the weighted pile-up kernel and a second table)
 int pileup_call(mc_ctx *c, const std::string &who, bool weighted, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus,
@@ -135,21 +158,8 @@ int pileup_call(mc_ctx *c, const std::string &who, bool weighted, const uint32_t
   TRY(check_ids(c, targets, nt));
   TRY(check_ids(c, a, m));
   TRY(check_ids(c, b, m));
-  constexpr uint32_t NO_TARGET = 0xffffffffu;
-  std::vector<uint32_t> tindex(c->n, NO_TARGET);  // point id -> its place among the targets
-  for (uint32_t t = 0; t < nt; t++) {
-    if (tindex[targets[t]] != NO_TARGET) {
-      set_error(who + ": point " + std::to_string(targets[t]) + " is listed twice among the targets");
-      return MC_ERR_ARG;
-    }
-    tindex[targets[t]] = t;
-  }
-  for (uint64_t i = 0; i < m; i++)
-    if (tindex[b[i]] == NO_TARGET) {
-      set_error(who + ": pair " + std::to_string(i) + "'s seq2, point " + std::to_string(b[i]) +
-                ", is not among the targets");
-      return MC_ERR_ARG;
-    }
+  std::vector<uint32_t> tindex;  // point id -> its place among the targets
+  TRY(index_targets(c, who, targets, nt, b, m, tindex));
   if (weighted) {  // a column's weight is at most MC_QUAL_MAX per pair: the sums must fit 32 bits
     std::vector<uint64_t> npairs(nt, 0);
     for (uint64_t i = 0; i < m; i++)
@@ -222,9 +232,218 @@ int pileup_call(mc_ctx *c, const std::string &who, bool weighted, const uint32_t
   return MC_OK;
 }
 
+// b grown to `bytes` with its first `keep` bytes kept (ensure() keeps nothing)
+int grow_keep(mc_ctx *c, Buf &b, size_t bytes, size_t keep) {
+  if (bytes <= b.bytes) return MC_OK;
+  Buf nb;
+  TRY(ensure(nb, std::max(bytes, 2 * b.bytes)));
+  hipError_t e = keep ? hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (no kernel still writes the old words)
+  if (e != hipSuccess) {
+    (void)hipFree(nb.p);
+    return hip_fail(e, "grow_keep");
+  }
+  if (b.p) (void)hipFree(b.p);
+  b = nb;
+  return MC_OK;
+}
+
+// rows [s0, s1) of mc_nw_msa_rows' numbering, all centre rows or all pair rows, rendered in batches
+// to out, one after the other
+int msa_render_rows(mc_ctx *c, bool centre, uint64_t s0, uint64_t s1, uint8_t *out) {
+  if (s0 >= s1) return MC_OK;
+  const uint64_t nt = c->msa_targets.size(), base = centre ? s0 : s0 - nt;
+  const uint32_t *ids = (centre ? c->msa_targets.data() : c->msa_a.data()) + base;
+  const uint8_t *minus = centre || c->msa_minus.empty() ? nullptr : c->msa_minus.data() + base;
+  auto target_of = [&](uint64_t i) { return centre ? base + i : (uint64_t)c->msa_tof[base + i]; };
+  mc::PairBatcher pb(c->h_seq_off.data(), c->n, ids, nullptr, minus, s1 - s0,
+                     {MC_IDENT_BATCH_PAIRS, env_cap("MC_IDENT_BYTES", MC_IDENT_BATCH_BYTES), env_cap("MC_MSA_BYTES", MC_MSA_BATCH_BYTES)});
+  pb.scratch_at = [&](uint64_t i) { return c->msa_W[target_of(i)]; };
+  std::vector<uint64_t> h_off;
+  std::vector<MsaRow> recs;
+  uint64_t done = 0;  // bytes of the rows before this batch
+  while (pb.next()) {
+    if (!pb.uniq.empty()) TRY(revseq_batch(c, pb.uniq.data(), (uint32_t)pb.uniq.size(), h_off));
+    recs.clear();
+    uint64_t bytes = 0;
+    for (uint64_t i = pb.i0; i < pb.i1; i++) {
+      const uint64_t t = target_of(i);
+      MsaRow r{};
+      r.out_off = bytes;
+      r.row0 = c->msa_row_off[t];
+      r.lb = (uint32_t)(c->msa_row_off[t + 1] - r.row0 - 1);
+      r.W = (uint32_t)c->msa_W[t];
+      if (centre) {
+        r.a_off = c->h_seq_off[c->msa_targets[t]];
+        r.la = r.lb;
+        r.nw = 1;
+        r.centre = 1;
+      } else {
+        const uint64_t p = base + i;
+        r.a_off = pb.minus(i) ? h_off[pb.slot(ids[i])] : c->h_seq_off[ids[i]];
+        r.la = (uint32_t)pb.length(ids[i]);
+        r.nw = c->msa_nops[p];
+        r.w_off = c->msa_woff[p];
+        r.a_rc = pb.minus(i) ? 1 : 0;
+      }
+      recs.push_back(r);
+      bytes += r.W;
+    }
+    if (bytes == 0) continue;
+    TRY(ensure(c->msa_out, bytes + 64));
+    TRY(upload(c, c->msa_rec, recs.data(), recs.size(), c->stream));
+    TRY(launch_msa_render(c, recs.size(), (const MsaRow *)c->msa_rec.p, (const uint8_t *)c->rc_seq.p, (const uint32_t *)c->msa_words.p,
+                          (const uint32_t *)c->msa_width.p, (const uint32_t *)c->msa_col.p, (uint8_t *)c->msa_out.p));
+    uint8_t *h = nullptr;  // through the pinned landing buffer while it stays small, else straight to out
+    if (bytes <= (64ull << 20)) TRY(download_pinned(c, c->msa_out.p, bytes, c->stream, &h));
+    if (h) {
+      memcpy(out + done, h, bytes);
+    } else {
+      MCG_CHECK(hipMemcpyAsync(out + done, c->msa_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
+      MCG_CHECK(hipStreamSynchronize(c->stream));
+    }
+    done += bytes;
+  }
+  return MC_OK;
+}
+
 }  // namespace
 
+namespace mcg {
+
+void msa_drop(mc_ctx *c) {
+  c->msa_on = false;
+  for (auto *v : {&c->msa_a, &c->msa_b, &c->msa_targets, &c->msa_tof, &c->msa_nops}) std::vector<uint32_t>().swap(*v);
+  for (auto *v : {&c->msa_woff, &c->msa_row_off, &c->msa_W}) std::vector<uint64_t>().swap(*v);
+  std::vector<uint8_t>().swap(c->msa_minus);
+}
+
+}  // namespace mcg
+
 extern "C" {
+
+int mc_nw_msa_begin(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m, const uint32_t *targets,
+                    uint32_t nt, uint64_t *row_off, uint32_t *width, uint64_t *block_width, int32_t *score, int32_t *len,
+                    int32_t *ids) {
+  if (c) msa_drop(c);
+  if (!c || !c->codes.p) return MC_ERR_STATE;
+  const std::string who = "mc_nw_msa_begin";
+  if (!row_off || !block_width || (nt && !targets) || (m && (!a || !b))) return MC_ERR_ARG;
+  MCG_CHECK(hipSetDevice(c->device));
+  TRY(check_ids(c, targets, nt));
+  TRY(check_ids(c, a, m));
+  TRY(check_ids(c, b, m));
+  std::vector<uint32_t> tindex;
+  TRY(index_targets(c, who, targets, nt, b, m, tindex));
+  TRY(align_check_caps(c, who.c_str(), a, b, m));
+  row_off[0] = 0;
+  for (uint32_t t = 0; t < nt; t++) row_off[t + 1] = row_off[t] + (c->h_seq_off[targets[t] + 1] - c->h_seq_off[targets[t]]) + 1;
+  const uint64_t rows = row_off[nt];
+  // the widths stay on the device for the whole call: zeroed once, every batch max-es into them
+  TRY(ensure(c->msa_width, rows * 4 + 64));
+  TRY(ensure(c->msa_col, rows * 4 + 64));
+  TRY(ensure(c->msa_bw, (uint64_t)nt * 8 + 64));
+  uint32_t *d_width = (uint32_t *)c->msa_width.p;
+  if (rows) MCG_CHECK(hipMemsetAsync(d_width, 0, rows * 4, c->stream));
+  std::vector<uint32_t> nops(m), tof(m);
+  std::vector<uint64_t> woff(m + 1, 0), dst, rowbase;
+  uint64_t total = 0;  // operation words packed so far
+  TRY(grow_keep(c, c->msa_words, 64, 0));
+  TRY(align_batches(c, who.c_str(), a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
+    scatter_res(res, i0, mb, score, len, ids);
+    dst.resize(mb);
+    rowbase.resize(mb);
+    const uint64_t before = total;
+    for (uint64_t k = 0; k < mb; k++) {
+      tof[i0 + k] = tindex[b[i0 + k]];
+      rowbase[k] = row_off[tof[i0 + k]];
+      nops[i0 + k] = (uint32_t)res[k * TRACE_RES + 3];
+      woff[i0 + k] = dst[k] = total;
+      total += nops[i0 + k];
+    }
+    // the batch's words behind those of the batches before it, in the plan's own buffer
+    TRY(grow_keep(c, c->msa_words, total * 4 + 64, before * 4));
+    TRY(upload(c, c->tr_dst, dst.data(), mb, c->stream));
+    TRY(upload(c, c->pu_rows, rowbase.data(), mb, c->stream));
+    TRY(launch_nw_pack(c, (uint32_t)mb, (const TracePair *)c->tr_pairs.p, (const uint32_t *)c->tr_ops.p, (const int32_t *)c->tr_res.p,
+                       (const uint64_t *)c->tr_dst.p, (uint32_t *)c->msa_words.p));
+    return launch_msa_width(c, (uint32_t)mb, (const TracePair *)c->tr_pairs.p, (const uint32_t *)c->tr_ops.p,
+                            (const int32_t *)c->tr_res.p, (const uint64_t *)c->pu_rows.p, d_width);
+  }));
+  woff[m] = total;
+  if (nt) {
+    TRY(upload(c, c->pu_roff, row_off, (size_t)nt + 1, c->stream));
+    TRY(launch_msa_columns(c, nt, (const uint64_t *)c->pu_roff.p, d_width, (uint32_t *)c->msa_col.p, (uint64_t *)c->msa_bw.p));
+    MCG_CHECK(hipMemcpyAsync(block_width, c->msa_bw.p, (size_t)nt * 8, hipMemcpyDeviceToHost, c->stream));
+    if (width && rows) MCG_CHECK(hipMemcpyAsync(width, d_width, rows * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  MCG_CHECK(hipStreamSynchronize(c->stream));
+  flush_timers(c);
+  for (uint32_t t = 0; t < nt; t++)
+    if (block_width[t] >= (1ull << 31)) {
+      set_error(who + ": target " + std::to_string(targets[t]) + "'s block is " + std::to_string(block_width[t]) +
+                " columns wide, the limit is 2^31 - 1");
+      return MC_ERR_UNSUPPORTED;
+    }
+  c->msa_a.assign(a, a + m);
+  c->msa_b.assign(b, b + m);
+  if (a_minus) c->msa_minus.assign(a_minus, a_minus + m);
+  c->msa_targets.assign(targets, targets + nt);
+  c->msa_row_off.assign(row_off, row_off + nt + 1);
+  c->msa_W.assign(block_width, block_width + nt);
+  c->msa_tof.swap(tof);
+  c->msa_nops.swap(nops);
+  c->msa_woff.swap(woff);
+  c->msa_on = true;
+  return MC_OK;
+}
+
+int mc_nw_msa_rows(mc_ctx *c, uint64_t first, uint64_t count, uint8_t *out, uint64_t cap, uint64_t *off) {
+  if (!c || !c->codes.p || !c->msa_on) return MC_ERR_STATE;
+  if (!off) return MC_ERR_ARG;
+  const uint64_t nt = c->msa_targets.size(), all = nt + c->msa_a.size();
+  if (first > all || count > all - first) {
+    set_error("mc_nw_msa_rows: rows " + std::to_string(first) + " .. " + std::to_string(first) + " + " + std::to_string(count) +
+              ", the plan has " + std::to_string(all));
+    return MC_ERR_ARG;
+  }
+  off[0] = 0;
+  for (uint64_t k = 0; k < count; k++) off[k + 1] = off[k] + c->msa_W[first + k < nt ? first + k : c->msa_tof[first + k - nt]];
+  if (!out || count == 0) return MC_OK;
+  if (cap < off[count]) {
+    set_error("mc_nw_msa_rows: out holds " + std::to_string(cap) + " bytes, the rows have " + std::to_string(off[count]));
+    return MC_ERR_ARG;
+  }
+  MCG_CHECK(hipSetDevice(c->device));
+  const uint64_t end = first + count, mid = std::min(std::max(first, nt), end);  // centre rows [first, mid), pair rows [mid, end)
+  TRY(msa_render_rows(c, true, first, mid, out));
+  TRY(msa_render_rows(c, false, mid, end, out + off[mid - first]));
+  flush_timers(c);
+  return MC_OK;
+}
+
+int mc_nw_msa_end(mc_ctx *c) {
+  if (!c) return MC_ERR_ARG;
+  msa_drop(c);
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  for (Buf *b : {&c->msa_width, &c->msa_col, &c->msa_words, &c->msa_bw, &c->msa_rec, &c->msa_out}) {
+    if (b->p) (void)hipFree(b->p);
+    *b = Buf{};
+  }
+  return MC_OK;
+}
+
+int mc_nw_msa_profile(mc_ctx *c, double *out, int reset) {
+  if (!c || !out) return MC_ERR_ARG;
+  (void)hipStreamSynchronize(c->stream);
+  flush_timers(c);
+  int k = 0;
+  for (int f : {F_NW_FWD, F_NW_TB, F_NW_MSAW, F_NW_MSAR}) out[k++] = c->fam_ms[f];
+  if (reset)
+    for (int f : {F_NW_FWD, F_NW_TB, F_NW_MSAW, F_NW_MSAR}) c->fam_ms[f] = c->fam_n[f] = 0;
+  return MC_OK;
+}
 
 int mc_revcomp_sequences(mc_ctx *c, const uint32_t *ids, uint64_t m, uint8_t *bytes, uint64_t *off) {
   if (!c || !c->codes.p) return MC_ERR_STATE;

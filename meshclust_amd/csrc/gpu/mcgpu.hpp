@@ -30,8 +30,9 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // F_LAYOUT: the static bvec-order copies of the rows (build_static), after K1
 // F_NW_FWD / F_NW_TB: the forward and traceback kernels of nwtrace.hip; they count as F_NW in
 // mc_timers and are kept apart only for mc_nw_align_profile; F_NW_PU: the pile-up kernels of
-// pileup.hip, likewise part of F_NW and kept apart for mc_nw_pileup_profile
-enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NALL };
+// pileup.hip, likewise part of F_NW and kept apart for mc_nw_pileup_profile; F_NW_MSAW / F_NW_MSAR:
+// the width + column kernels and the render kernel of msa.hip, part of F_NW, for mc_nw_msa_profile
+enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NALL };
 
 // Classifier in the form the kernels consume (mc_classifier + the exact decision threshold).
 struct DevClassifier {
@@ -95,6 +96,15 @@ struct TracePair {
   uint32_t la, lb, a_rc, r;
 };
 constexpr int TRACE_RES = 5;  // per pair: score, columns, identities, operation words, final state
+
+// One row of a render batch of mc_nw_msa_rows (msa.hip): W bytes at out_off of the batch's output;
+// seq1 at a_off of the minus-strand buffer (a_rc) or of the loaded codes; its nw operation words at
+// w_off of the plan's words (centre: none, the row is one '=' run of lb over the centre's own bytes);
+// row0: the first of its target's lb + 1 widths and columns.
+struct MsaRow {
+  uint64_t out_off, a_off, w_off, row0;
+  uint32_t la, lb, nw, W, a_rc, centre;
+};
 
 // A range of one array of the device lazy introsort (split.hip): partitioned (left >= 0:
 // children left, left + 1, cut between them) or finished (fin: a sorted leaf).
@@ -190,6 +200,16 @@ struct mc_ctx {
   // mc_nw_qpileup_strands: the call's weight table and a batch's read offset per pair
   mcg::Buf qual, pu_wtable, pu_qoff;
   bool has_qual = false;
+  // mc_nw_msa_begin's plan, kept until the next begin, mc_nw_msa_end or a load of
+  // sequences.  On the device, owned by the plan and touched by no other entry: a width and a column
+  // per pile-up row (uint32), every pair's packed operation words.  On the host: the pairs, every
+  // pair's target, word count and word offset, the targets, their row offsets and block widths.
+  // msa_rec / msa_out: a render batch's row records and rendered bytes (mc_nw_msa_rows only).
+  bool msa_on = false;
+  mcg::Buf msa_width, msa_col, msa_words, msa_bw, msa_rec, msa_out;
+  std::vector<uint32_t> msa_a, msa_b, msa_targets, msa_tof, msa_nops;
+  std::vector<uint8_t> msa_minus;
+  std::vector<uint64_t> msa_woff, msa_row_off, msa_W;
   // mc_update_iteration's member lists on the device and their host shadow: re-uploaded only
   // when a merge changed them (cleared when sequences are loaded: the ids were checked against n)
   mcg::Buf u_off, u_mem;
@@ -309,6 +329,17 @@ int launch_nw_pileup_finish(mc_ctx *c, uint32_t nt, const uint64_t *d_tgt_off, c
 int launch_nw_qpileup(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint8_t *d_rc, const uint32_t *d_ops,
                       const int32_t *d_res, const uint64_t *d_rowbase, const uint64_t *d_qoff, uint32_t *d_table,
                       uint32_t *d_wtable, int32_t *d_deq, int32_t *d_ddel);
+
+// msa.hip (mc_nw_msa_*): per pair of a batch (after launch_nw_trace) the length of every 'I' run
+// max-ed into d_width[d_rowbase[p] + row]; per target the columns d_col and the block width d_bw
+// from the widths; a render batch's rows (d_rows, nrows of them) into d_out.
+int launch_msa_width(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint32_t *d_ops, const int32_t *d_res,
+                     const uint64_t *d_rowbase, uint32_t *d_width);
+int launch_msa_columns(mc_ctx *c, uint32_t nt, const uint64_t *d_row_off, const uint32_t *d_width, uint32_t *d_col, uint64_t *d_bw);
+int launch_msa_render(mc_ctx *c, uint64_t nrows, const MsaRow *d_rows, const uint8_t *d_rc, const uint32_t *d_words,
+                      const uint32_t *d_width, const uint32_t *d_col, uint8_t *d_out);
+// abi_align.hip: forget mc_nw_msa_begin's plan (its device buffers stay for the next one)
+void msa_drop(mc_ctx *c);
 
 }  // namespace mcg
 

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 
 #ifdef _OPENMP
 #include <omp.h>
@@ -26,7 +27,7 @@ namespace mc {
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
     "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--consensus FILE] "
-    "[--pileup FILE] [--quality] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
+    "[--pileup FILE] [--quality] [--msa FILE] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
     "                  (implied by a version-2 model, saved by meshclust --both-strands: reads and centres are then\n"
     "                  scored once on their canonical rows and every hit's strand comes from mc_orient_pairs; with\n"
@@ -49,6 +50,9 @@ static const char *kUsage =
     "                  a column goes to the channel of the largest summed Phred value, the consensus is written as\n"
     "                  FASTQ (@NAME depth=D sub=S del=X ins=I) with a quality per base, the pile-up rows gain wA wC wG\n"
     "                  wT wN wdel\n"
+    "  --msa FILE      (implies --identity) the assigned reads of every centre laid out in common columns, as aligned\n"
+    "                  FASTA: >CENTRE depth=D width=W and the centre's row, then >READ strand=+ (or -) and its row per\n"
+    "                  read; inserted bases get columns of their own, gaps are -\n"
     "  reads and centres may be FASTA or FASTQ files (decided per file); without --quality the qualities are skipped\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
@@ -91,6 +95,9 @@ AssignOptions parse_assign_options(int argc, char **argv) {
       o.identity = true;
     } else if (arg == "--quality") {
       o.quality = true;
+    } else if (arg == "--msa" && has) {
+      o.msa = argv[++i];
+      o.identity = true;
     } else {
       struct stat st;
       if (stat(argv[i], &st) == 0 && S_ISREG(st.st_mode)) o.reads.push_back(argv[i]);
@@ -312,6 +319,101 @@ static void pileup_outputs(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std
   }
   if (!opt.consensus.empty()) write_text(opt.consensus, fa);
   if (!opt.pileup.empty()) write_text(opt.pileup, tsv);
+}
+
+// --msa: the pairs (read pa, centre pb < C, strand pm) of the assigned reads, sorted by centre (input
+// order kept), through one mc_nw_msa_begin with the centres that have a read as targets; the rows
+// come back through two windows of at most 32 MiB, one over the centre rows and one over the pair
+// rows, and are written block by block.
+static void msa_output(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::vector<uint32_t> &pa, const std::vector<uint32_t> &pb,
+                       const std::vector<uint8_t> &pm, const AssignOptions &opt, AssignResult &r) {
+  const size_t m = pa.size();
+  std::vector<uint64_t> from((size_t)C + 1, 0);  // a centre's pairs after the sort: from[c] .. from[c + 1]
+  for (size_t p = 0; p < m; p++) from[pb[p] + 1]++;
+  for (uint32_t j = 0; j < C; j++) from[j + 1] += from[j];
+  std::vector<uint32_t> qa(m), qb(m), targets;
+  std::vector<uint8_t> qm(m);
+  {
+    std::vector<uint64_t> at(from.begin(), from.end() - 1);
+    for (size_t p = 0; p < m; p++) {
+      const uint64_t k = at[pb[p]]++;
+      qa[k] = pa[p], qb[k] = pb[p], qm[k] = pm[p];
+    }
+  }
+  std::vector<uint32_t> tof(m);  // a sorted pair's place among the targets
+  for (uint32_t j = 0; j < C; j++)
+    if (from[j + 1] > from[j]) {
+      std::fill(tof.begin() + from[j], tof.begin() + from[j + 1], (uint32_t)targets.size());
+      targets.push_back(j);
+    }
+  const uint32_t nt = (uint32_t)targets.size();
+  std::vector<uint64_t> row_off((size_t)nt + 1), W(nt);
+  check(mc_nw_msa_begin(ctx, qa.data(), qb.data(), qm.data(), m, targets.data(), nt, row_off.data(), nullptr, W.data(), nullptr, nullptr,
+                        nullptr),
+        "mc_nw_msa_begin");
+  struct End {
+    mc_ctx *c;
+    ~End() { mc_nw_msa_end(c); }
+  } ender{ctx};
+  r.msa = true;
+  r.msa_pairs = m;
+  r.msa_centres = nt;
+  FILE *f = fopen(opt.msa.c_str(), "w");
+  if (!f) throw Error("cannot write " + opt.msa + ": " + strerror(errno), 1);
+  struct Close {
+    FILE *&f;
+    ~Close() {
+      if (f) fclose(f);
+    }
+  } closer{f};
+  // a window over rows [lo, hi) of mc_nw_msa_rows' numbering; width_of(row) is the row's W
+  const uint64_t kWindow = 32ull << 20;
+  struct Window {
+    uint64_t lo = 0, hi = 0;
+    std::vector<uint8_t> bytes;
+    std::vector<uint64_t> off;
+  } win[2];
+  auto row = [&](Window &w, uint64_t k, uint64_t end, const std::function<uint64_t(uint64_t)> &width_of) -> const uint8_t * {
+    if (k >= w.hi) {  // the rows from k on that fit the window (one at least)
+      uint64_t n = 0, sum = 0;
+      while (k + n < end && (n == 0 || sum + width_of(k + n) <= kWindow)) sum += width_of(k + n++);
+      w.bytes.resize(sum);
+      w.off.resize(n + 1);
+      check(mc_nw_msa_rows(ctx, k, n, w.bytes.data(), sum, w.off.data()), "mc_nw_msa_rows");
+      w.lo = k;
+      w.hi = k + n;
+    }
+    return w.bytes.data() + w.off[k - w.lo];
+  };
+  std::string text;
+  char num[96];
+  auto flush = [&](bool all) {
+    if (text.size() < (all ? 1u : 1u << 20)) return;
+    if (fwrite(text.data(), 1, text.size(), f) != text.size()) throw Error("cannot write " + opt.msa, 1);
+    text.clear();
+  };
+  for (uint32_t t = 0; t < nt; t++) {
+    const uint32_t j = targets[t];
+    const uint64_t depth = from[j + 1] - from[j];
+    r.msa_columns += W[t];
+    r.msa_bytes += (depth + 1) * W[t];
+    text.append(ds.headers[j]);
+    snprintf(num, sizeof num, " depth=%llu width=%llu\n", (unsigned long long)depth, (unsigned long long)W[t]);
+    text += num;
+    text.append((const char *)row(win[0], t, nt, [&](uint64_t k) { return W[k]; }), W[t]);
+    text += '\n';
+    for (uint64_t k = from[j]; k < from[j + 1]; k++) {
+      text.append(ds.headers[qa[k]]);
+      text += qm[k] ? " strand=-\n" : " strand=+\n";
+      text.append((const char *)row(win[1], nt + k, nt + m, [&](uint64_t x) { return W[tof[x - nt]]; }), W[t]);
+      text += '\n';
+      flush(false);
+    }
+  }
+  flush(true);
+  FILE *done = f;
+  f = nullptr;
+  if (fclose(done) != 0) throw Error("cannot write " + opt.msa, 1);
 }
 
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
@@ -603,6 +705,19 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
     }
   }
   r.identity_ms = ms_since(t0);
+  if (!opt.msa.empty()) {  // a pass of its own, over the pairs --consensus takes
+    t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> pa, pb;
+    std::vector<uint8_t> pm;
+    for (uint64_t q = 0; q < M; q++)
+      if (best[q] != MC_ASSIGN_NONE) {
+        pa.push_back((uint32_t)(C + q));
+        pb.push_back(best[q]);
+        pm.push_back(opt.both_strands ? strand[q] : 0);
+      }
+    msa_output(ctx, ds, (uint32_t)C, pa, pb, pm, opt, r);
+    r.msa_ms = ms_since(t0);
+  }
   t0 = std::chrono::steady_clock::now();
   // one line per read, in input order: read header, centre header or *, cluster index or -1,
   // combo 0, similar centres (headers without their '>'); with both strands a sixth column: the
@@ -670,7 +785,7 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
 
 std::string assign_stats_json(const AssignResult &r) {
   // (one strand, no --top, no --identity: exactly the keys there were before any of the options)
-  char b[1536], s[704] = "", idms[48] = "";
+  char b[1792], s[704] = "", idms[48] = "", msa[224] = "", msams[48] = "";
   int n = 0;
   if (r.strands != MC_STRAND_PLUS)
     n = snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
@@ -689,14 +804,20 @@ std::string assign_stats_json(const AssignResult &r) {
                (unsigned long long)r.realigned_centres, (unsigned long long)r.insertion_sites, r.quality ? "\"quality\": 1, " : "");
     snprintf(idms, sizeof idms, "\"identity\": %.3f, ", r.identity_ms);
   }
+  if (r.msa) {  // after every key there was before --msa
+    snprintf(msa, sizeof msa, ", \"msa_pairs\": %llu, \"msa_centres\": %llu, \"msa_columns\": %llu, \"msa_bytes\": %llu",
+             (unsigned long long)r.msa_pairs, (unsigned long long)r.msa_centres, (unsigned long long)r.msa_columns,
+             (unsigned long long)r.msa_bytes);
+    snprintf(msams, sizeof msams, ", \"msa\": %.3f", r.msa_ms);
+  }
   snprintf(b, sizeof b,
            "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, %s\"k\": %d, \"width\": %d, "
            "\"path\": \"%s\", \"candidate_pairs\": %llu, \"fallback_pairs\": %llu, \"device_us\": %llu, "
-           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f}}",
+           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f%s}%s}",
            (unsigned long long)r.reads, (unsigned long long)r.centres, (unsigned long long)r.assigned,
            (unsigned long long)(r.reads - r.assigned), s, r.k, r.width, r.path.c_str(), (unsigned long long)r.candidates,
            (unsigned long long)r.fallbacks, (unsigned long long)r.device_us, r.parse_ms, r.upload_ms, r.kmer_ms,
-           r.assign_ms, idms, r.write_ms);
+           r.assign_ms, idms, r.write_ms, msams, msa);
   return b;
 }
 

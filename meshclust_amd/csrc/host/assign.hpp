@@ -23,6 +23,7 @@ struct AssignOptions {
   std::string consensus;      // --consensus FILE (implies identity): a consensus per centre from its assigned reads, FASTA
   std::string pileup;         // --pileup FILE (implies the consensus pass): the per-column counts behind it, TSV
   bool quality = false;       // --quality (with consensus and/or pileup; FASTQ reads): the pile-up weighed by base quality
+  std::string msa;            // --msa FILE (implies identity): every centre's reads laid out in common columns, aligned FASTA
 };
 
 struct AssignResult {
@@ -44,8 +45,10 @@ struct AssignResult {
   int consensus_passes = 0;                             // centres re-aligned for their inserted bases, sites applied
   uint64_t realigned_centres = 0, insertion_sites = 0;
   bool quality = false;          // --quality: the qualities were uploaded and the weighted pile-up ran
+  bool msa = false;              // --msa: pairs laid out, centres with a read, the sum of their widths, bytes of all rows
+  uint64_t msa_pairs = 0, msa_centres = 0, msa_columns = 0, msa_bytes = 0;
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
-  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0;
+  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0, msa_ms = 0;
 };
 
 // Throws mc::Error (bad options: code 1 with the usage text in what()).
@@ -92,6 +95,14 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // FASTQ ("@NAME depth=D sub=S del=X ins=I", sequence, "+", a quality per base; consensus.hpp
 // qconsensus_of; a centre without reads: its own sequence at '!'), every pileup row gains the six
 // weights wA wC wG wT wN wdel, and the stats "quality": 1.
+// With msa (implies identity; a pass of its own after every other, which changes none of their
+// outputs) the pairs consensus takes -- (read, final centre, strand) of every assigned read -- are
+// sorted by centre and go through one mc_nw_msa_begin; the rows are streamed to the file in chunks
+// of at most 64 MiB.  The file is aligned FASTA, one block per centre that has a read, in
+// centres-file order: ">CENTRE depth=D width=W" and the centre's row, then per read in input order
+// ">READ strand=+" (or -) and its row; every row of a block is W characters, gaps '-'.  The stats
+// gain, after every other key, "msa_pairs", "msa_centres", "msa_columns" (the sum of W) and
+// "msa_bytes" (the sum of rows * W), and the phases "msa".
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
 std::string assign_stats_json(const AssignResult &r);
 int assign_main(int argc, char **argv);

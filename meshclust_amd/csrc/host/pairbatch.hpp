@@ -4,7 +4,8 @@
 // and a batch keeps one minus-strand string per such read, padded to 16 bytes.  Start a batch at
 // i0 and take pair i1 while i1 < m and i1 - i0 < caps.pairs, with two stops:
 //   - caps.scratch != 0: stop before pair i1 when i1 > i0 and the batch's scratch plus
-//     scratch_of(la, lb) would exceed caps.scratch;
+//     scratch_of(la, lb) would exceed caps.scratch (scratch_at(i1) where it is set: a need that
+//     the two lengths do not give, the width of mc_nw_msa_rows' row i1);
 //   - pair i1 is minus and its read has no slot in this batch yet: stop before it when the batch
 //     already holds a minus string and its padded bytes plus (la + 15) / 16 * 16 would exceed
 //     caps.bytes.
@@ -40,6 +41,7 @@ class PairBatcher {
   uint64_t i0 = 0, i1 = 0;     // the current batch, [i0, i1)
   uint64_t nminus = 0;         // its minus pairs
   std::vector<uint32_t> uniq;  // the reads whose minus-strand strings it needs: uniq[slot(id)] == id
+  std::function<uint64_t(uint64_t)> scratch_at;  // if set: pair i's scratch, in place of scratch_of (b may then be empty)
 
   uint64_t length(uint32_t id) const { return off_[id + 1] - off_[id]; }
   bool minus(uint64_t i) const { return minus_ && minus_[i]; }
@@ -54,7 +56,7 @@ class PairBatcher {
     uint64_t pad = 0, scr = 0;
     while (i1 < m_ && i1 - i0 < caps_.pairs) {
       const uint64_t la = length(a_[i1]);
-      const uint64_t need = caps_.scratch ? scratch_of_(la, length(b_[i1])) : 0;
+      const uint64_t need = !caps_.scratch ? 0 : scratch_at ? scratch_at(i1) : scratch_of_(la, length(b_[i1]));
       if (caps_.scratch && i1 > i0 && scr + need > caps_.scratch) break;
       const bool is_minus = minus(i1);
       if (is_minus && slot_[a_[i1]] == NO_SLOT) {
