@@ -542,6 +542,58 @@ int mc_nw_msa_end(mc_ctx *ctx);
 int mc_nw_msa_profile(mc_ctx *ctx, double *out /* 4 */, int reset);
 
 /*
+ * THE COLUMN PROFILE of the multiple alignment: every column of a block counted on the device, so
+ * that 32 bytes per column come back instead of one byte per row and column.  mc_nw_msa_counts works
+ * on the plan of the last mc_nw_msa_begin, for targets first_target .. first_target + ntargets in
+ * the plan's target order.  Target t owns W_t columns (begin's block_width) of MC_MSA_CH counters;
+ * col_off (ntargets + 1, required) receives the prefix sums of W_t.  In begin's terms, with depth the
+ * number of the target's pairs and the class of a byte x being x for x <= 3, else 4:
+ *   the column of centre base r (col[r], r < L)
+ *       channels 0..5   row r, channels 0..5, of mc_nw_pileup_strands' table for the same pairs, bit
+ *                       for bit: 0..4 the reads' bytes by class, 5 the reads with a 'D'
+ *       channel 6       r;  channel 7: 0
+ *   slot t (0-based) of site r (column col[r] - w[r] + t, r = 0 .. L, t < w[r])
+ *       channel c <= 4  the pairs whose 'I' run at r is longer than t and whose inserted byte
+ *                       seq1[i + t] has class c
+ *       channel 5       depth less the sum of channels 0..4: the rows that hold a gap there
+ *       channel 6       r;  channel 7: t + 1
+ * Invariants: channels 0..5 of every column add up to depth; channel 5 of slot 0 equals depth less
+ * pile-up channel 6 of row r; over a site's slots the sum of channels 0..4 is pile-up channel 7 of
+ * row r; a target without pairs has L columns of zeros apart from channel 6; the counts are integers,
+ * so nothing depends on the pair order, the batches or the split of targets over calls; the counts
+ * equal the per-column histogram of the pair rows mc_nw_msa_rows renders (the centre row is not
+ * counted; a read byte above 3 that is itself one of the characters A C G T - is class 4 here, as in
+ * the pile-up, and shows as that character there).
+ * wcounts, the same shape, holds weights from mc_load_qualities (Qs as for mc_nw_qpileup_strands):
+ *   centre column r   channels 0..5 equal mc_nw_qpileup_strands' wtable row r, channels 0..5,
+ *                     its rule for 'D' included
+ *   slot t of site r  channel c <= 4: the sum of Qs(i + t) over the pairs counted in counts'
+ *                     channel c; channel 5: 0
+ *   channels 6 and 7  0 everywhere
+ * counts and wcounts both NULL: the offsets only, no device work.  wcounts alone non-NULL:
+ * MC_ERR_ARG.  wcounts non-NULL with no qualities loaded: MC_ERR_STATE.  Either non-NULL with
+ * cap_cols < col_off[ntargets]: MC_ERR_ARG, col_off valid, nothing written.  A range past the plan's
+ * nt: MC_ERR_ARG.  No plan: MC_ERR_STATE.  ntargets = 0: MC_OK.  With wcounts, a target of more than
+ * (2^32 - 1) / MC_QUAL_MAX = 46,182,038 pairs: MC_ERR_ARG.  All of these are found before any launch.
+ * The tables are overwritten, not added to; the plan is unchanged, so rows and counts may be called
+ * in any order and any number of times.
+ * Device: the targets go in batches whose column tables (a context-owned buffer) stay within
+ * MC_MSA_BATCH_BYTES (MC_MSA_BYTES lowers it; a wider target is taken alone); the pairs of a batch of
+ * targets in batches of minus-strand strings as mc_nw_msa_rows' (MC_IDENT_BYTES).  A wavefront per pair
+ * walks the plan's operation words: two atomics per '=' or 'D' run on per-centre difference arrays,
+ * one per mismatched column and per inserted base on the column table; with wcounts one more per
+ * column (a lane walks a run of at most 8 columns, longer runs are taken by the whole wave).  A
+ * wavefront per target then turns the differences into counts, writes channels 6 and 7 and every
+ * slot's gap count, with no atomics.  Nothing is aligned again.  Timed as "nw", the reverse
+ * complement as "layout".  mc_nw_msa_counts_profile: out[0] = device ms of the counts kernels since
+ * the last reset; mc_nw_msa_profile's four values do not include them.
+ */
+#define MC_MSA_CH 8
+int mc_nw_msa_counts(mc_ctx *ctx, uint32_t first_target, uint32_t ntargets, uint64_t *col_off /* ntargets + 1, required */,
+                     uint32_t *counts, uint32_t *wcounts /* each col_off[ntargets] * MC_MSA_CH */, uint64_t cap_cols);
+int mc_nw_msa_counts_profile(mc_ctx *ctx, double *out /* 1 */, int reset);
+
+/*
  * Accumulation (ClusterFactory::accumulate, ClusterFactory.cpp:637-714).
  * The bvec of Runner.cpp:342-350 is only ever shrunk after insert_finalize, so the device
  * holds one static candidate order (bin-major, length-sorted within bins) plus an alive

@@ -35,6 +35,7 @@ ERR_STATE = 3
 CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # MC_CIGAR_*: mc_nw_align_strands' words are run << 4 | op
 PILEUP_CH = 8  # MC_PILEUP_CH: counters per row of mc_nw_pileup_strands' table
 MSA_GAP = ord("-")  # MC_MSA_GAP: the gap byte of mc_nw_msa_rows
+MSA_CH = 8  # MC_MSA_CH: counters per column of mc_nw_msa_counts
 QUAL_MAX = 93  # MC_QUAL_MAX: the largest Phred value mc_load_qualities takes
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
@@ -139,6 +140,10 @@ def gpu_lib():
         lib.mc_nw_msa_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.mc_nw_msa_end.argtypes = [C.c_void_p]
         lib.mc_nw_msa_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.mc_nw_msa_counts.restype = C.c_int
+        lib.mc_nw_msa_counts.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.mc_nw_msa_counts_profile.restype = C.c_int
+        lib.mc_nw_msa_counts_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _bind_steps(lib)
         _gpu = lib
     return _gpu
@@ -228,6 +233,10 @@ def host_lib():
         lib.mcl_assign_msa.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                        C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
                                        C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
+        lib.mcl_assign_profile.restype = C.c_int
+        lib.mcl_assign_profile.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                           C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
+                                           C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -738,6 +747,33 @@ class Engine:
         self._ck(self.lib.mc_nw_msa_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_msa_profile")
         return tuple(float(x) for x in out)
 
+    def nw_msa_counts(self, first, count, weights=False, counts=True):
+        """mc_nw_msa_counts: the column profile of targets first .. first + count of the plan ->
+        (col_off, counts[columns, 8]) or, with ``weights`` (qualities loaded), (col_off, counts, wcounts).
+        Target t's columns are col_off[t] .. col_off[t + 1].  counts: channels 0..4 the rows' bytes by
+        class (A C G T other), 5 the rows with a gap, 6 the centre position or insertion site r, 7 zero
+        for a centre column and the 1-based slot for an inserted one; the centre row is not counted.
+        wcounts: the qualities summed over the same bytes (channel 5 of a centre column: the deletions'
+        weights as in nw_qpileup_strands; channels 6 and 7 zero).  ``counts=False``: (col_off,) only, no
+        device work."""
+        off = np.zeros(count + 1, np.uint64)
+        self._ck(self.lib.mc_nw_msa_counts(self.ctx, C.c_uint32(first), C.c_uint32(count), _p(off), None, None, C.c_uint64(0)),
+                 "mc_nw_msa_counts")
+        if not counts:
+            return (off,)
+        cols = int(off[-1])
+        tab = np.zeros((cols, MSA_CH), np.uint32)
+        wtab = np.zeros((cols, MSA_CH), np.uint32) if weights else None
+        self._ck(self.lib.mc_nw_msa_counts(self.ctx, C.c_uint32(first), C.c_uint32(count), _p(off), _p(tab), _p(wtab), C.c_uint64(cols)),
+                 "mc_nw_msa_counts")
+        return (off, tab, wtab) if weights else (off, tab)
+
+    def nw_msa_counts_profile(self, reset=False):
+        """mc_nw_msa_counts_profile -> device ms of nw_msa_counts' kernels since the last reset."""
+        out = np.zeros(1)
+        self._ck(self.lib.mc_nw_msa_counts_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_msa_counts_profile")
+        return float(out[0])
+
     def nw_identity_raw(self, a_cat, a_off, b_cat, b_off):
         a_cat = np.ascontiguousarray(a_cat, np.uint8)
         b_cat = np.ascontiguousarray(b_cat, np.uint8)
@@ -763,7 +799,7 @@ class Engine:
 
 
 def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None,
-                 identity=False, min_identity=None, paf=None, consensus=None, pileup=None, quality=False, msa=None):
+                 identity=False, min_identity=None, paf=None, consensus=None, pileup=None, quality=False, msa=None, profile=None):
     """Place the reads of the FASTA or FASTQ file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
@@ -793,13 +829,25 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     ``msa``: meshclust-assign's --msa FILE (mcl_assign_msa; implies ``identity``): the assigned reads of every centre
     laid out in common columns (mc_nw_msa_begin / mc_nw_msa_rows) as aligned FASTA, a pass of its own that changes
     no other output; the stats gain, last, ``msa_pairs``, ``msa_centres``, ``msa_columns``, ``msa_bytes`` and the
-    ``msa`` phase."""
+    ``msa`` phase.
+    ``profile``: meshclust-assign's --profile FILE (mcl_assign_profile; implies ``identity``): that alignment counted
+    per column (mc_nw_msa_counts; one mc_nw_msa_begin shared with ``msa``) as a TSV, one line per column of every
+    centre with reads: centre, column, centre_pos, slot, base, depth, A, C, G, T, N, gap, and with ``quality`` (then
+    accepted beside ``profile`` alone) wA wC wG wT wN wgap; the stats gain, last, ``profile_centres``,
+    ``profile_columns`` and the ``profile`` phase."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    if msa is not None:
+    if profile is not None:
+        rc = lib.mcl_assign_profile(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                    unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
+                                    hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),
+                                    paf.encode() if paf else None, consensus.encode() if consensus else None,
+                                    pileup.encode() if pileup else None, 1 if quality else 0, msa.encode() if msa else None,
+                                    profile.encode(), buf, len(buf))
+    elif msa is not None:
         rc = lib.mcl_assign_msa(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                 unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
                                 hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),

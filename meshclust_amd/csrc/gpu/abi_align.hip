@@ -313,8 +313,8 @@ namespace mcg {
 
 void msa_drop(mc_ctx *c) {
   c->msa_on = false;
-  for (auto *v : {&c->msa_a, &c->msa_b, &c->msa_targets, &c->msa_tof, &c->msa_nops}) std::vector<uint32_t>().swap(*v);
-  for (auto *v : {&c->msa_woff, &c->msa_row_off, &c->msa_W}) std::vector<uint64_t>().swap(*v);
+  for (auto *v : {&c->msa_a, &c->msa_b, &c->msa_targets, &c->msa_tof, &c->msa_nops, &c->msa_tp}) std::vector<uint32_t>().swap(*v);
+  for (auto *v : {&c->msa_woff, &c->msa_row_off, &c->msa_W, &c->msa_tp_off}) std::vector<uint64_t>().swap(*v);
   std::vector<uint8_t>().swap(c->msa_minus);
 }
 
@@ -394,6 +394,15 @@ int mc_nw_msa_begin(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8
   c->msa_tof.swap(tof);
   c->msa_nops.swap(nops);
   c->msa_woff.swap(woff);
+  // every target's pairs in list order (mc_nw_msa_counts walks the plan by target)
+  c->msa_tp_off.assign((size_t)nt + 1, 0);
+  for (uint64_t i = 0; i < m; i++) c->msa_tp_off[c->msa_tof[i] + 1]++;
+  for (uint32_t t = 0; t < nt; t++) c->msa_tp_off[t + 1] += c->msa_tp_off[t];
+  c->msa_tp.resize(m);
+  {
+    std::vector<uint64_t> at(c->msa_tp_off.begin(), c->msa_tp_off.end() - 1);
+    for (uint64_t i = 0; i < m; i++) c->msa_tp[at[c->msa_tof[i]]++] = (uint32_t)i;
+  }
   c->msa_on = true;
   return MC_OK;
 }
@@ -422,12 +431,142 @@ int mc_nw_msa_rows(mc_ctx *c, uint64_t first, uint64_t count, uint8_t *out, uint
   return MC_OK;
 }
 
+int mc_nw_msa_counts(mc_ctx *c, uint32_t first, uint32_t ntg, uint64_t *col_off, uint32_t *counts, uint32_t *wcounts,
+                     uint64_t cap_cols) {
+  if (!c || !c->codes.p || !c->msa_on) return MC_ERR_STATE;
+  const std::string who = "mc_nw_msa_counts";
+  if (!col_off) return MC_ERR_ARG;
+  const uint64_t nt = c->msa_targets.size();
+  if (first > nt || ntg > nt - first) {
+    set_error(who + ": targets " + std::to_string(first) + " .. " + std::to_string(first) + " + " + std::to_string(ntg) +
+              ", the plan has " + std::to_string(nt));
+    return MC_ERR_ARG;
+  }
+  if (wcounts && !counts) {
+    set_error(who + ": wcounts is given with counts (both NULL: the offsets only)");
+    return MC_ERR_ARG;
+  }
+  if (wcounts && !c->has_qual) {
+    set_error(who + ": no qualities are loaded (mc_load_qualities)");
+    return MC_ERR_STATE;
+  }
+  const uint64_t end = (uint64_t)first + ntg;
+  if (wcounts)  // a column's weight is at most MC_QUAL_MAX per pair: the sums must fit 32 bits
+    for (uint64_t t = first; t < end; t++)
+      if (c->msa_tp_off[t + 1] - c->msa_tp_off[t] > 0xffffffffull / MC_QUAL_MAX) {
+        set_error(who + ": target " + std::to_string(c->msa_targets[t]) + " has more than " +
+                  std::to_string(0xffffffffull / MC_QUAL_MAX) + " pairs, its weights would not fit 32 bits");
+        return MC_ERR_ARG;
+      }
+  col_off[0] = 0;
+  for (uint64_t k = 0; k < ntg; k++) col_off[k + 1] = col_off[k] + c->msa_W[first + k];
+  if (!counts || ntg == 0) return MC_OK;
+  if (cap_cols < col_off[ntg]) {
+    set_error(who + ": the tables hold " + std::to_string(cap_cols) + " columns, the targets have " + std::to_string(col_off[ntg]));
+    return MC_ERR_ARG;
+  }
+  MCG_CHECK(hipSetDevice(c->device));
+  const uint64_t col_bytes = (uint64_t)MC_MSA_CH * 4 * (wcounts ? 2 : 1), cap = env_cap("MC_MSA_BYTES", MC_MSA_BATCH_BYTES);
+  const uint64_t ident_cap = env_cap("MC_IDENT_BYTES", MC_IDENT_BATCH_BYTES);
+  std::vector<MsaCountTarget> tgts;
+  std::vector<MsaCountPair> recs;
+  std::vector<uint32_t> ids;
+  std::vector<uint8_t> minus;
+  std::vector<uint64_t> h_off;
+  for (uint64_t t0 = first, t1; t0 < end; t0 = t1) {
+    // a batch of targets: it ends before the target that would take its tables past the cap (a wider one is taken alone)
+    uint64_t cols = 0;
+    for (t1 = t0; t1 < end && (t1 == t0 || (cols + c->msa_W[t1]) * col_bytes <= cap); t1++) cols += c->msa_W[t1];
+    if (cols == 0) continue;
+    const uint64_t rows = c->msa_row_off[t1] - c->msa_row_off[t0];
+    TRY(ensure(c->msa_cnt, cols * MC_MSA_CH * 4 + 64));
+    TRY(ensure(c->msa_cdiff, rows * 8 + 64));
+    uint32_t *d_cnt = (uint32_t *)c->msa_cnt.p, *d_wcnt = nullptr;
+    int32_t *d_deq = (int32_t *)c->msa_cdiff.p, *d_ddel = d_deq + rows;
+    MCG_CHECK(hipMemsetAsync(d_cnt, 0, cols * MC_MSA_CH * 4, c->stream));
+    MCG_CHECK(hipMemsetAsync(d_deq, 0, rows * 8, c->stream));
+    if (wcounts) {
+      TRY(ensure(c->msa_wcnt, cols * MC_MSA_CH * 4 + 64));
+      d_wcnt = (uint32_t *)c->msa_wcnt.p;
+      MCG_CHECK(hipMemsetAsync(d_wcnt, 0, cols * MC_MSA_CH * 4, c->stream));
+    }
+    tgts.clear();
+    for (uint64_t t = t0; t < t1; t++) {
+      MsaCountTarget g{};
+      g.c_off = c->h_seq_off[c->msa_targets[t]];
+      g.row0 = c->msa_row_off[t];
+      g.col0 = col_off[t - first] - col_off[t0 - first];
+      g.drow0 = c->msa_row_off[t] - c->msa_row_off[t0];
+      g.L = (uint32_t)(c->msa_row_off[t + 1] - g.row0 - 1);
+      g.W = (uint32_t)c->msa_W[t];
+      g.depth = (uint32_t)(c->msa_tp_off[t + 1] - c->msa_tp_off[t]);
+      tgts.push_back(g);
+    }
+    // the batch's pairs, target by target; their minus-strand strings in batches as mc_nw_msa_rows'
+    const uint32_t *pidx = c->msa_tp.data() + c->msa_tp_off[t0];
+    const uint64_t np = c->msa_tp_off[t1] - c->msa_tp_off[t0];
+    ids.resize(np);
+    minus.resize(np);
+    for (uint64_t i = 0; i < np; i++) {
+      ids[i] = c->msa_a[pidx[i]];
+      minus[i] = c->msa_minus.empty() ? 0 : c->msa_minus[pidx[i]];
+    }
+    mc::PairBatcher pb(c->h_seq_off.data(), c->n, ids.data(), nullptr, c->msa_minus.empty() ? nullptr : minus.data(), np,
+                       {MC_IDENT_BATCH_PAIRS, ident_cap, 0});
+    while (pb.next()) {
+      if (!pb.uniq.empty()) TRY(revseq_batch(c, pb.uniq.data(), (uint32_t)pb.uniq.size(), h_off));
+      recs.clear();
+      for (uint64_t i = pb.i0; i < pb.i1; i++) {
+        const uint64_t p = pidx[i];
+        const MsaCountTarget &g = tgts[c->msa_tof[p] - t0];
+        MsaCountPair r{};
+        r.a_off = pb.minus(i) ? h_off[pb.slot(ids[i])] : c->h_seq_off[ids[i]];
+        r.w_off = c->msa_woff[p];
+        r.row0 = g.row0;
+        r.col0 = g.col0;
+        r.drow0 = g.drow0;
+        r.q_off = c->h_seq_off[ids[i]];
+        r.la = (uint32_t)pb.length(ids[i]);
+        r.lb = g.L;
+        r.nw = c->msa_nops[p];
+        r.W = g.W;
+        r.a_rc = pb.minus(i) ? 1 : 0;
+        recs.push_back(r);
+      }
+      TRY(upload(c, c->msa_crec, recs.data(), recs.size(), c->stream));
+      TRY(launch_msa_counts(c, recs.size(), (const MsaCountPair *)c->msa_crec.p, (const uint8_t *)c->rc_seq.p,
+                            (const uint32_t *)c->msa_words.p, (const uint32_t *)c->msa_width.p, (const uint32_t *)c->msa_col.p, d_cnt,
+                            d_wcnt, d_deq, d_ddel));
+      MCG_CHECK(hipStreamSynchronize(c->stream));  // (the records and the strings' offsets are reused by the next batch)
+    }
+    TRY(upload(c, c->msa_ctgt, tgts.data(), tgts.size(), c->stream));
+    TRY(launch_msa_counts_finish(c, (uint32_t)tgts.size(), (const MsaCountTarget *)c->msa_ctgt.p, (const uint32_t *)c->msa_width.p,
+                                 (const uint32_t *)c->msa_col.p, d_cnt, d_deq, d_ddel));
+    const uint64_t at = (col_off[t0 - first]) * MC_MSA_CH;
+    MCG_CHECK(hipMemcpyAsync(counts + at, d_cnt, cols * MC_MSA_CH * 4, hipMemcpyDeviceToHost, c->stream));
+    if (wcounts) MCG_CHECK(hipMemcpyAsync(wcounts + at, d_wcnt, cols * MC_MSA_CH * 4, hipMemcpyDeviceToHost, c->stream));
+    MCG_CHECK(hipStreamSynchronize(c->stream));
+  }
+  flush_timers(c);
+  return MC_OK;
+}
+
+int mc_nw_msa_counts_profile(mc_ctx *c, double *out, int reset) {
+  if (!c || !out) return MC_ERR_ARG;
+  (void)hipStreamSynchronize(c->stream);
+  flush_timers(c);
+  out[0] = c->fam_ms[F_NW_MSAC];
+  if (reset) c->fam_ms[F_NW_MSAC] = c->fam_n[F_NW_MSAC] = 0;
+  return MC_OK;
+}
+
 int mc_nw_msa_end(mc_ctx *c) {
   if (!c) return MC_ERR_ARG;
   msa_drop(c);
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  for (Buf *b : {&c->msa_width, &c->msa_col, &c->msa_words, &c->msa_bw, &c->msa_rec, &c->msa_out}) {
+  for (Buf *b : {&c->msa_width, &c->msa_col, &c->msa_words, &c->msa_bw, &c->msa_rec, &c->msa_out, &c->msa_cnt, &c->msa_wcnt,
+                 &c->msa_cdiff, &c->msa_crec, &c->msa_ctgt}) {
     if (b->p) (void)hipFree(b->p);
     *b = Buf{};
   }

@@ -31,8 +31,9 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // F_NW_FWD / F_NW_TB: the forward and traceback kernels of nwtrace.hip; they count as F_NW in
 // mc_timers and are kept apart only for mc_nw_align_profile; F_NW_PU: the pile-up kernels of
 // pileup.hip, likewise part of F_NW and kept apart for mc_nw_pileup_profile; F_NW_MSAW / F_NW_MSAR:
-// the width + column kernels and the render kernel of msa.hip, part of F_NW, for mc_nw_msa_profile
-enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NALL };
+// the width + column kernels and the render kernel of msa.hip, part of F_NW, for mc_nw_msa_profile;
+// F_NW_MSAC: the counts kernels of msa.hip (mc_nw_msa_counts), part of F_NW, for mc_nw_msa_counts_profile
+enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NW_MSAC, F_NALL };
 
 // Classifier in the form the kernels consume (mc_classifier + the exact decision threshold).
 struct DevClassifier {
@@ -104,6 +105,22 @@ constexpr int TRACE_RES = 5;  // per pair: score, columns, identities, operation
 struct MsaRow {
   uint64_t out_off, a_off, w_off, row0;
   uint32_t la, lb, nw, W, a_rc, centre;
+};
+
+// One pair of a counts batch of mc_nw_msa_counts (msa.hip): seq1 and its words as in MsaRow; row0:
+// the first of its target's lb + 1 widths and columns in the plan; col0 / drow0: where the target's
+// W columns and lb + 1 difference entries start in the batch's tables; q_off: the read's offset in
+// the loaded qualities (as loaded, whatever the strand).
+struct MsaCountPair {
+  uint64_t a_off, w_off, row0, col0, drow0, q_off;
+  uint32_t la, lb, nw, W, a_rc, pad;
+};
+
+// One target of a counts batch: its centre's bytes at c_off of the loaded codes, row0 / col0 / drow0
+// as in MsaCountPair, L bytes, W columns, depth pairs.
+struct MsaCountTarget {
+  uint64_t c_off, row0, col0, drow0;
+  uint32_t L, W, depth, pad;
 };
 
 // A range of one array of the device lazy introsort (split.hip): partitioned (left >= 0:
@@ -205,9 +222,13 @@ struct mc_ctx {
   // per pile-up row (uint32), every pair's packed operation words.  On the host: the pairs, every
   // pair's target, word count and word offset, the targets, their row offsets and block widths.
   // msa_rec / msa_out: a render batch's row records and rendered bytes (mc_nw_msa_rows only).
+  // msa_tp_off / msa_tp: every target's pairs in list order (nt + 1 offsets into m pair indices).
+  // msa_cnt / msa_wcnt / msa_cdiff / msa_crec / msa_ctgt: a counts batch's column tables, its two
+  // difference arrays, pair records and target records (mc_nw_msa_counts only).
   bool msa_on = false;
-  mcg::Buf msa_width, msa_col, msa_words, msa_bw, msa_rec, msa_out;
-  std::vector<uint32_t> msa_a, msa_b, msa_targets, msa_tof, msa_nops;
+  mcg::Buf msa_width, msa_col, msa_words, msa_bw, msa_rec, msa_out, msa_cnt, msa_wcnt, msa_cdiff, msa_crec, msa_ctgt;
+  std::vector<uint32_t> msa_a, msa_b, msa_targets, msa_tof, msa_nops, msa_tp;
+  std::vector<uint64_t> msa_tp_off;
   std::vector<uint8_t> msa_minus;
   std::vector<uint64_t> msa_woff, msa_row_off, msa_W;
   // mc_update_iteration's member lists on the device and their host shadow: re-uploaded only
@@ -338,6 +359,15 @@ int launch_msa_width(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint
 int launch_msa_columns(mc_ctx *c, uint32_t nt, const uint64_t *d_row_off, const uint32_t *d_width, uint32_t *d_col, uint64_t *d_bw);
 int launch_msa_render(mc_ctx *c, uint64_t nrows, const MsaRow *d_rows, const uint8_t *d_rc, const uint32_t *d_words,
                       const uint32_t *d_width, const uint32_t *d_col, uint8_t *d_out);
+// the pairs of a counts batch (d_pairs, npairs of them) added to the batch's column table d_counts
+// (MC_MSA_CH counters per column) and difference arrays d_deq / d_ddel; d_wcounts given: the loaded
+// qualities summed beside them.  launch_msa_counts_finish: per target of the batch the differences
+// turned into counts, channels 6 and 7, and every slot's gap count.
+int launch_msa_counts(mc_ctx *c, uint64_t npairs, const MsaCountPair *d_pairs, const uint8_t *d_rc, const uint32_t *d_words,
+                      const uint32_t *d_width, const uint32_t *d_col, uint32_t *d_counts, uint32_t *d_wcounts, int32_t *d_deq,
+                      int32_t *d_ddel);
+int launch_msa_counts_finish(mc_ctx *c, uint32_t nt, const MsaCountTarget *d_tgts, const uint32_t *d_width, const uint32_t *d_col,
+                             uint32_t *d_counts, const int32_t *d_deq, const int32_t *d_ddel);
 // abi_align.hip: forget mc_nw_msa_begin's plan (its device buffers stay for the next one)
 void msa_drop(mc_ctx *c);
 

@@ -27,6 +27,21 @@
 // SPREAD gaps, are taken one after the other by the whole wave, 64 bytes per step.  Every trip
 // count is known on entry.  A run that would leave the pair's strings is skipped and no byte at or
 // past W is stored, so no address outside the row is formed.
+//
+// msa_counts_kernel / msa_counts_finish_kernel (mc_nw_msa_counts): the block counted
+// per column instead of rendered, MC_MSA_CH counters per column.  A wavefront per pair, the same walk:
+//   '=' / 'D' run of n at row j   +1 at j and -1 at j + n of the target's '=' / 'D' difference array
+//                                 (pileup.hip's two atomics per run)
+//   'X' run of n at row j         per column one atomic on the class of seq1[i + t] at col[j + t]
+//   'I' run of n at row j         per base one atomic on its class at col[j] - w[j] + t
+// WEIGHTED: beside them the loaded qualities into a second table, an atomic per column as
+// nwt_pileup_kernel<false, true> does ('=' and 'X' the base's quality, 'D' the smaller quality around
+// the gap on channel 5, 'I' the inserted base's own quality in its slot); a zero weight issues none.
+// A lane walks a run of at most SPREAD columns itself, longer runs are taken by the whole wave.  The
+// finish kernel, a wavefront per target and no atomics: the running sums of the differences go to
+// col[r] (the centre byte's class, channel 5), channels 6 and 7 are written, and every slot's
+// channel 5 becomes depth less its channels 0..4.  A run that would leave the pair's strings is
+// skipped and no column at or past W is touched: msa_render_kernel's rule.
 #include "mcgpu.hpp"
 
 namespace mcg {
@@ -203,6 +218,152 @@ __global__ __launch_bounds__(64) void msa_render_kernel(const MsaRow *__restrict
   }
 }
 
+__device__ __forceinline__ uint32_t base_class(uint8_t x) { return x <= 3 ? x : 4u; }
+
+struct CountArgs {
+  const MsaCountPair *pairs;
+  uint32_t npairs;
+  const uint8_t *codes, *rc, *qual;
+  const uint32_t *words, *width, *col;
+  uint32_t *counts, *wcounts;
+  int32_t *deq, *ddel;
+};
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(64) void msa_counts_kernel(CountArgs q) {
+  const uint32_t p = blockIdx.x;
+  if (p >= q.npairs) return;
+  const MsaCountPair pr = q.pairs[p];
+  const uint8_t *a = (pr.a_rc ? q.rc : q.codes) + pr.a_off;
+  const uint8_t *ql = WEIGHTED ? q.qual + pr.q_off : nullptr;
+  const uint32_t *w = q.width + pr.row0, *col = q.col + pr.row0;
+  const uint32_t *src = q.words + pr.w_off;
+  uint32_t *tab = q.counts + pr.col0 * MC_MSA_CH, *wt = WEIGHTED ? q.wcounts + pr.col0 * MC_MSA_CH : nullptr;
+  int32_t *deq = q.deq + pr.drow0, *ddel = q.ddel + pr.drow0;
+  const uint32_t la = pr.la, L = pr.lb, W = pr.W, nw = pr.nw;
+  const bool rc = pr.a_rc != 0;
+  const int lane = (int)threadIdx.x;
+  auto Qs = [&](uint32_t i) -> uint32_t { return ql[rc ? la - 1 - i : i]; };  // i < la
+  auto gapq = [&](uint32_t i) -> uint32_t {  // nwt_pileup_kernel's weight of a 'D' run with i read bases before it
+    uint32_t v = 0xffffffffu;
+    if (i > 0) v = Qs(i - 1);
+    if (i < la) v = min(v, Qs(i));
+    return v == 0xffffffffu ? 0u : v;
+  };
+  auto add = [&](uint32_t pc, uint32_t ch) {
+    if (pc < W) atomicAdd(&tab[(uint64_t)pc * MC_MSA_CH + ch], 1u);
+  };
+  auto addw = [&](uint32_t pc, uint32_t ch, uint32_t v) {
+    if (WEIGHTED && v && pc < W) atomicAdd(&wt[(uint64_t)pc * MC_MSA_CH + ch], v);
+  };
+  // column t of a run: op, the read position i0 and row j0 it starts at, s0 the first slot of an 'I'
+  // run's site, gq a 'D' run's weight
+  auto column = [&](uint32_t op, uint32_t i0, uint32_t j0, uint32_t s0, uint32_t gq, uint32_t t) {
+    if (op == MC_CIGAR_D) {
+      addw(col[j0 + t], 5u, gq);
+      return;
+    }
+    const uint32_t ch = base_class(a[i0 + t]), pc = op == MC_CIGAR_I ? s0 + t : col[j0 + t];
+    if (op != MC_CIGAR_EQ) add(pc, ch);
+    if (WEIGHTED) addw(pc, ch, Qs(i0 + t));
+  };
+  uint32_t ci = 0, cj = 0;  // bases consumed before this chunk
+  const uint32_t nchunk = (nw + 63) / 64;
+  for (uint32_t c = 0; c < nchunk; c++) {
+    const uint32_t kk = c * 64 + (uint32_t)lane;
+    const uint32_t wd = kk < nw ? src[kk] : 0u;
+    const uint32_t n = wd >> 4, op = wd & 15u;
+    const bool both = op == MC_CIGAR_EQ || op == MC_CIGAR_X, del = op == MC_CIGAR_D, ins = op == MC_CIGAR_I;
+    const uint32_t di = both || ins ? n : 0u, dj = both || del ? n : 0u;
+    const uint32_t si = wave_scan(di, lane), sj = wave_scan(dj, lane);
+    const uint32_t i0 = ci + si - di, j0 = cj + sj - dj;
+    ci += (uint32_t)__shfl((int)si, 63, 64);
+    cj += (uint32_t)__shfl((int)sj, 63, 64);
+    const bool ok = n > 0 && i0 + di <= la && j0 + dj <= L && (both || del || ins);
+    if (ok && op == MC_CIGAR_EQ) {
+      atomicAdd(&deq[j0], 1);
+      atomicAdd(&deq[j0 + n], -1);
+    } else if (ok && del) {
+      atomicAdd(&ddel[j0], 1);
+      atomicAdd(&ddel[j0 + n], -1);
+    }
+    // the columns that take an atomic each: cnt of them (an 'I' run: no more than its site has slots)
+    uint32_t cnt = 0, s0 = 0, gq = 0;
+    if (ok && ins) {
+      const uint32_t wj = w[j0];
+      s0 = col[j0] - wj;
+      cnt = min(n, wj);
+    } else if (ok && (op == MC_CIGAR_X || WEIGHTED)) {
+      cnt = n;
+      if (WEIGHTED && del) {
+        gq = gapq(i0);
+        if (!gq) cnt = 0;
+      }
+    }
+    if (cnt <= SPREAD)
+      for (uint32_t t = 0; t < cnt; t++) column(op, i0, j0, s0, gq, t);
+    unsigned long long wide = __ballot(cnt > SPREAD);
+    while (wide) {  // (wave-uniform: one turn per long run of this chunk)
+      const int s = __ffsll(wide) - 1;
+      wide &= wide - 1;
+      const uint32_t bi = (uint32_t)__shfl((int)i0, s, 64), bj = (uint32_t)__shfl((int)j0, s, 64);
+      const uint32_t bs = (uint32_t)__shfl((int)s0, s, 64), bg = (uint32_t)__shfl((int)gq, s, 64);
+      const uint32_t bn = (uint32_t)__shfl((int)cnt, s, 64), bop = (uint32_t)__shfl((int)op, s, 64);
+      for (uint32_t t = (uint32_t)lane; t < bn; t += 64) column(bop, bi, bj, bs, bg, t);
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void msa_counts_finish_kernel(const MsaCountTarget *__restrict__ tgts, uint32_t nt,
+                                                               const uint8_t *__restrict__ codes, const uint32_t *__restrict__ width,
+                                                               const uint32_t *__restrict__ colarr, uint32_t *__restrict__ counts,
+                                                               const int32_t *__restrict__ deq_all, const int32_t *__restrict__ ddel_all) {
+  const uint32_t k = blockIdx.x;
+  if (k >= nt) return;
+  const MsaCountTarget tg = tgts[k];
+  const uint8_t *b = codes + tg.c_off;
+  const uint32_t *w = width + tg.row0, *col = colarr + tg.row0;
+  uint32_t *tab = counts + tg.col0 * MC_MSA_CH;
+  const int32_t *deq = deq_all + tg.drow0, *ddel = ddel_all + tg.drow0;
+  const uint32_t L = tg.L, W = tg.W, depth = tg.depth;
+  const int lane = (int)threadIdx.x;
+  auto slot = [&](uint32_t pc, uint32_t r, uint32_t t) {  // slot t of site r: the rows with a gap, the site, the slot
+    if (pc >= W) return;
+    uint32_t *row = tab + (uint64_t)pc * MC_MSA_CH;
+    row[5] = depth - (row[0] + row[1] + row[2] + row[3] + row[4]);
+    row[6] = r;
+    row[7] = t + 1;
+  };
+  uint32_t ce = 0, cd = 0;  // coverage carried into this chunk
+  const uint32_t nchunk = L / 64 + 1;  // rows 0 .. L
+  for (uint32_t c = 0; c < nchunk; c++) {
+    const uint32_t r = c * 64 + (uint32_t)lane;
+    const bool base = r < L, site = r <= L;
+    const uint32_t e = base ? (uint32_t)deq[r] : 0u, d = base ? (uint32_t)ddel[r] : 0u;
+    const uint32_t se = ce + wave_scan(e, lane), sd = cd + wave_scan(d, lane);
+    ce = (uint32_t)__shfl((int)se, 63, 64);
+    cd = (uint32_t)__shfl((int)sd, 63, 64);
+    const uint32_t pc = site ? col[r] : 0u, wr = site ? w[r] : 0u;
+    if (base && pc < W) {
+      uint32_t *row = tab + (uint64_t)pc * MC_MSA_CH;
+      if (se) row[base_class(b[r])] += se;
+      if (sd) row[5] += sd;
+      row[6] = r;
+      row[7] = 0;
+    }
+    if (wr <= SPREAD)
+      for (uint32_t t = 0; t < wr; t++) slot(pc - wr + t, r, t);
+    unsigned long long wide = __ballot(wr > SPREAD);
+    while (wide) {  // (wave-uniform: one turn per wide site of this chunk)
+      const int s = __ffsll(wide) - 1;
+      wide &= wide - 1;
+      const uint32_t bc = (uint32_t)__shfl((int)pc, s, 64), bw = (uint32_t)__shfl((int)wr, s, 64);
+      const uint32_t br = c * 64 + (uint32_t)s;
+      for (uint32_t t = (uint32_t)lane; t < bw; t += 64) slot(bc - bw + t, br, t);
+    }
+  }
+}
+
 }  // namespace
 
 int launch_msa_width(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint32_t *d_ops, const int32_t *d_res,
@@ -232,6 +393,30 @@ int launch_msa_render(mc_ctx *c, uint64_t nrows, const MsaRow *d_rows, const uin
                                                            d_col, d_out);
   MCG_CHECK(hipGetLastError());
   timed_end(c, F_NW_MSAR);
+  return MC_OK;
+}
+
+int launch_msa_counts(mc_ctx *c, uint64_t npairs, const MsaCountPair *d_pairs, const uint8_t *d_rc, const uint32_t *d_words,
+                      const uint32_t *d_width, const uint32_t *d_col, uint32_t *d_counts, uint32_t *d_wcounts, int32_t *d_deq,
+                      int32_t *d_ddel) {
+  if (npairs == 0) return MC_OK;
+  CountArgs q{d_pairs, (uint32_t)npairs, (const uint8_t *)c->codes.p, d_rc, (const uint8_t *)c->qual.p, d_words, d_width, d_col,
+              d_counts, d_wcounts, d_deq, d_ddel};
+  timed_begin(c);
+  if (d_wcounts) msa_counts_kernel<true><<<(unsigned)npairs, 64, 0, c->stream>>>(q);
+  else msa_counts_kernel<false><<<(unsigned)npairs, 64, 0, c->stream>>>(q);
+  MCG_CHECK(hipGetLastError());
+  timed_end(c, F_NW_MSAC);
+  return MC_OK;
+}
+
+int launch_msa_counts_finish(mc_ctx *c, uint32_t nt, const MsaCountTarget *d_tgts, const uint32_t *d_width, const uint32_t *d_col,
+                             uint32_t *d_counts, const int32_t *d_deq, const int32_t *d_ddel) {
+  if (nt == 0) return MC_OK;
+  timed_begin(c);
+  msa_counts_finish_kernel<<<nt, 64, 0, c->stream>>>(d_tgts, nt, (const uint8_t *)c->codes.p, d_width, d_col, d_counts, d_deq, d_ddel);
+  MCG_CHECK(hipGetLastError());
+  timed_end(c, F_NW_MSAC);
   return MC_OK;
 }
 

@@ -27,7 +27,7 @@ namespace mc {
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
     "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--consensus FILE] "
-    "[--pileup FILE] [--quality] [--msa FILE] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
+    "[--pileup FILE] [--quality] [--msa FILE] [--profile FILE] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
     "                  (implied by a version-2 model, saved by meshclust --both-strands: reads and centres are then\n"
     "                  scored once on their canonical rows and every hit's strand comes from mc_orient_pairs; with\n"
@@ -53,6 +53,9 @@ static const char *kUsage =
     "  --msa FILE      (implies --identity) the assigned reads of every centre laid out in common columns, as aligned\n"
     "                  FASTA: >CENTRE depth=D width=W and the centre's row, then >READ strand=+ (or -) and its row per\n"
     "                  read; inserted bases get columns of their own, gaps are -\n"
+    "  --profile FILE  (implies --identity) that alignment counted per column, for centres with reads: centre, column,\n"
+    "                  centre_pos, slot (0: a centre base; from 1: an inserted column before it), base (- inserted),\n"
+    "                  depth, A, C, G, T, N, gap; with --quality (FASTQ reads) also wA wC wG wT wN wgap\n"
     "  reads and centres may be FASTA or FASTQ files (decided per file); without --quality the qualities are skipped\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
@@ -98,6 +101,9 @@ AssignOptions parse_assign_options(int argc, char **argv) {
     } else if (arg == "--msa" && has) {
       o.msa = argv[++i];
       o.identity = true;
+    } else if (arg == "--profile" && has) {
+      o.profile = argv[++i];
+      o.identity = true;
     } else {
       struct stat st;
       if (stat(argv[i], &st) == 0 && S_ISREG(st.st_mode)) o.reads.push_back(argv[i]);
@@ -107,8 +113,8 @@ AssignOptions parse_assign_options(int argc, char **argv) {
   if (o.model.empty() || o.centres.empty() || o.reads.empty())
     throw Error(std::string("--model, --centres and at least one reads file are required\n") + kUsage, 1);
   if ((o.top > 0) != !o.hits.empty()) throw Error(std::string("--top K and --hits FILE are given together\n") + kUsage, 1);
-  if (o.quality && o.consensus.empty() && o.pileup.empty())
-    throw Error(std::string("--quality needs --consensus FILE and/or --pileup FILE\n") + kUsage, 1);
+  if (o.quality && o.consensus.empty() && o.pileup.empty() && o.profile.empty())
+    throw Error(std::string("--quality needs --consensus FILE and/or --pileup FILE (or --profile FILE)\n") + kUsage, 1);
   return o;
 }
 
@@ -321,10 +327,71 @@ static void pileup_outputs(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std
   if (!opt.pileup.empty()) write_text(opt.pileup, tsv);
 }
 
-// --msa: the pairs (read pa, centre pb < C, strand pm) of the assigned reads, sorted by centre (input
-// order kept), through one mc_nw_msa_begin with the centres that have a read as targets; the rows
-// come back through two windows of at most 32 MiB, one over the centre rows and one over the pair
-// rows, and are written block by block.
+// --profile: the plan of msa_output counted per column (mc_nw_msa_counts), read in ranges of targets
+// whose tables stay within 64 MiB on the host (a wider target alone), one line per column.
+static void profile_output(mc_ctx *ctx, const Dataset &ds, const std::vector<uint32_t> &targets, const std::vector<uint64_t> &W,
+                           const std::vector<uint64_t> &depth, const AssignOptions &opt, AssignResult &r) {
+  const uint32_t nt = (uint32_t)targets.size();
+  const uint64_t col_bytes = (uint64_t)MC_MSA_CH * 4 * (opt.quality ? 2 : 1), kWindow = 64ull << 20;
+  r.profile = true;
+  r.profile_centres = nt;
+  FILE *f = fopen(opt.profile.c_str(), "w");
+  if (!f) throw Error("cannot write " + opt.profile + ": " + strerror(errno), 1);
+  struct Close {
+    FILE *&f;
+    ~Close() {
+      if (f) fclose(f);
+    }
+  } closer{f};
+  std::string text;
+  char num[256];
+  auto flush = [&](bool all) {
+    if (text.size() < (all ? 1u : 1u << 20)) return;
+    if (fwrite(text.data(), 1, text.size(), f) != text.size()) throw Error("cannot write " + opt.profile, 1);
+    text.clear();
+  };
+  std::vector<uint32_t> counts, wcounts;
+  std::vector<uint64_t> off;
+  for (uint32_t t0 = 0, t1; t0 < nt; t0 = t1) {
+    uint64_t cols = 0;
+    for (t1 = t0; t1 < nt && (t1 == t0 || (cols + W[t1]) * col_bytes <= kWindow); t1++) cols += W[t1];
+    counts.resize(cols * MC_MSA_CH);
+    if (opt.quality) wcounts.resize(cols * MC_MSA_CH);
+    off.resize((size_t)(t1 - t0) + 1);
+    check(mc_nw_msa_counts(ctx, t0, t1 - t0, off.data(), counts.data(), opt.quality ? wcounts.data() : nullptr, cols), "mc_nw_msa_counts");
+    for (uint32_t t = t0; t < t1; t++) {
+      const uint32_t j = targets[t];
+      const std::vector<uint8_t> cen = expanded_bytes(ds, j);
+      const std::string name(ds.headers[j].substr(1));
+      for (uint64_t c = 0; c < W[t]; c++) {
+        const uint32_t *x = counts.data() + (off[t - t0] + c) * MC_MSA_CH;
+        text.append(name);
+        snprintf(num, sizeof num, "\t%llu\t%u\t%u\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u", (unsigned long long)(c + 1), x[6] + 1, x[7],
+                 x[7] == 0 && x[6] < cen.size() ? pileup_base_char(cen[x[6]]) : '-', (unsigned long long)depth[t], x[0], x[1], x[2], x[3],
+                 x[4], x[5]);
+        text += num;
+        if (opt.quality) {
+          const uint32_t *y = wcounts.data() + (off[t - t0] + c) * MC_MSA_CH;
+          snprintf(num, sizeof num, "\t%u\t%u\t%u\t%u\t%u\t%u", y[0], y[1], y[2], y[3], y[4], y[5]);
+          text += num;
+        }
+        text += '\n';
+      }
+      r.profile_columns += W[t];
+      flush(false);
+    }
+  }
+  flush(true);
+  FILE *done = f;
+  f = nullptr;
+  if (fclose(done) != 0) throw Error("cannot write " + opt.profile, 1);
+}
+
+// --msa / --profile: the pairs (read pa, centre pb < C, strand pm) of the assigned reads, sorted by
+// centre (input order kept), through one mc_nw_msa_begin with the centres that have a read as
+// targets.  --msa: the rows come back through two windows of at most 32 MiB, one over the centre rows
+// and one over the pair rows, and are written block by block.  --profile: profile_output on the same
+// plan; beside --msa its time goes to r.profile_ms.
 static void msa_output(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::vector<uint32_t> &pa, const std::vector<uint32_t> &pb,
                        const std::vector<uint8_t> &pm, const AssignOptions &opt, AssignResult &r) {
   const size_t m = pa.size();
@@ -355,6 +422,12 @@ static void msa_output(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::ve
     mc_ctx *c;
     ~End() { mc_nw_msa_end(c); }
   } ender{ctx};
+  std::vector<uint64_t> depths(nt);
+  for (uint32_t t = 0; t < nt; t++) depths[t] = from[targets[t] + 1] - from[targets[t]];
+  if (opt.msa.empty()) {  // --profile alone (the caller times the whole pass)
+    profile_output(ctx, ds, targets, W, depths, opt, r);
+    return;
+  }
   r.msa = true;
   r.msa_pairs = m;
   r.msa_centres = nt;
@@ -414,6 +487,11 @@ static void msa_output(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::ve
   FILE *done = f;
   f = nullptr;
   if (fclose(done) != 0) throw Error("cannot write " + opt.msa, 1);
+  if (!opt.profile.empty()) {
+    const auto t0 = std::chrono::steady_clock::now();
+    profile_output(ctx, ds, targets, W, depths, opt, r);
+    r.profile_ms = ms_since(t0);
+  }
 }
 
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
@@ -705,7 +783,7 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
     }
   }
   r.identity_ms = ms_since(t0);
-  if (!opt.msa.empty()) {  // a pass of its own, over the pairs --consensus takes
+  if (!opt.msa.empty() || !opt.profile.empty()) {  // a pass of its own, over the pairs --consensus takes
     t0 = std::chrono::steady_clock::now();
     std::vector<uint32_t> pa, pb;
     std::vector<uint8_t> pm;
@@ -716,7 +794,8 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
         pm.push_back(opt.both_strands ? strand[q] : 0);
       }
     msa_output(ctx, ds, (uint32_t)C, pa, pb, pm, opt, r);
-    r.msa_ms = ms_since(t0);
+    if (r.msa) r.msa_ms = ms_since(t0) - r.profile_ms;  // (the begin counts with the first output)
+    else r.profile_ms = ms_since(t0);
   }
   t0 = std::chrono::steady_clock::now();
   // one line per read, in input order: read header, centre header or *, cluster index or -1,
@@ -785,7 +864,7 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
 
 std::string assign_stats_json(const AssignResult &r) {
   // (one strand, no --top, no --identity: exactly the keys there were before any of the options)
-  char b[1792], s[704] = "", idms[48] = "", msa[224] = "", msams[48] = "";
+  char b[1920], s[704] = "", idms[48] = "", msa[224] = "", msams[48] = "", prof[128] = "", profms[48] = "";
   int n = 0;
   if (r.strands != MC_STRAND_PLUS)
     n = snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
@@ -810,14 +889,19 @@ std::string assign_stats_json(const AssignResult &r) {
              (unsigned long long)r.msa_bytes);
     snprintf(msams, sizeof msams, ", \"msa\": %.3f", r.msa_ms);
   }
+  if (r.profile) {  // after every key there was before --profile
+    snprintf(prof, sizeof prof, ", \"profile_centres\": %llu, \"profile_columns\": %llu", (unsigned long long)r.profile_centres,
+             (unsigned long long)r.profile_columns);
+    snprintf(profms, sizeof profms, ", \"profile\": %.3f", r.profile_ms);
+  }
   snprintf(b, sizeof b,
            "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, %s\"k\": %d, \"width\": %d, "
            "\"path\": \"%s\", \"candidate_pairs\": %llu, \"fallback_pairs\": %llu, \"device_us\": %llu, "
-           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f%s}%s}",
+           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f%s%s}%s%s}",
            (unsigned long long)r.reads, (unsigned long long)r.centres, (unsigned long long)r.assigned,
            (unsigned long long)(r.reads - r.assigned), s, r.k, r.width, r.path.c_str(), (unsigned long long)r.candidates,
            (unsigned long long)r.fallbacks, (unsigned long long)r.device_us, r.parse_ms, r.upload_ms, r.kmer_ms,
-           r.assign_ms, idms, r.write_ms, msams, msa);
+           r.assign_ms, idms, r.write_ms, msams, profms, msa, prof);
   return b;
 }
 

@@ -24,6 +24,7 @@ struct AssignOptions {
   std::string pileup;         // --pileup FILE (implies the consensus pass): the per-column counts behind it, TSV
   bool quality = false;       // --quality (with consensus and/or pileup; FASTQ reads): the pile-up weighed by base quality
   std::string msa;            // --msa FILE (implies identity): every centre's reads laid out in common columns, aligned FASTA
+  std::string profile;        // --profile FILE (implies identity): the column profile of every centre's alignment, TSV
 };
 
 struct AssignResult {
@@ -47,8 +48,10 @@ struct AssignResult {
   bool quality = false;          // --quality: the qualities were uploaded and the weighted pile-up ran
   bool msa = false;              // --msa: pairs laid out, centres with a read, the sum of their widths, bytes of all rows
   uint64_t msa_pairs = 0, msa_centres = 0, msa_columns = 0, msa_bytes = 0;
+  bool profile = false;          // --profile: centres with a read, the columns written
+  uint64_t profile_centres = 0, profile_columns = 0;
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
-  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0, msa_ms = 0;
+  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0, msa_ms = 0, profile_ms = 0;
 };
 
 // Throws mc::Error (bad options: code 1 with the usage text in what()).
@@ -89,7 +92,7 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // Centres with an insertion site are re-aligned with mc_nw_align_strands for the inserted bases
 // ("realigned_centres").
 // Reads and centres may be FASTA or FASTQ files (fasta.hpp); the qualities are skipped unless
-// quality is set, which needs consensus and/or pileup (parse_assign_options: usage error) and every
+// quality is set, which needs consensus, pileup or profile (parse_assign_options: usage error) and every
 // reads file to be FASTQ (Error of code 2 naming the file).  The qualities are then uploaded
 // (mc_load_qualities), the pile-up pass goes through mc_nw_qpileup_strands, consensus is written as
 // FASTQ ("@NAME depth=D sub=S del=X ins=I", sequence, "+", a quality per base; consensus.hpp
@@ -103,6 +106,14 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // ">READ strand=+" (or -) and its row; every row of a block is W characters, gaps '-'.  The stats
 // gain, after every other key, "msa_pairs", "msa_centres", "msa_columns" (the sum of W) and
 // "msa_bytes" (the sum of rows * W), and the phases "msa".
+// With profile (implies identity; it shares msa's mc_nw_msa_begin when both are given and changes no
+// other output) the same plan is counted per column by mc_nw_msa_counts, read in ranges of targets
+// of at most 64 MiB.  The file is a TSV, for centres with a read, in centres-file order, one line per
+// column: centre, column (from 1), centre_pos, slot, base, depth, A, C, G, T, N, gap.  A centre's own
+// column has centre_pos r + 1, slot 0 and the centre's character; an inserted column has the site
+// r + 1 (L + 1 after the last base), slot t + 1 and base '-'.  With quality (then also accepted
+// beside profile alone) every line gains wA wC wG wT wN wgap.  The stats gain, after every other
+// key, "profile_centres" and "profile_columns", and the phases "profile".
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
 std::string assign_stats_json(const AssignResult &r);
 int assign_main(int argc, char **argv);
