@@ -407,6 +407,47 @@ int mc_nw_align_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, const
 int mc_nw_align_profile(mc_ctx *ctx, double *out /* 3 */, int reset);
 
 /*
+ * THE CERTIFIED BAND: a smaller choice record for the same alignments.  The forward pass above
+ * records 4 bits for every cell of the la x lb matrix; the chain of a read against its centre stays
+ * near the main diagonal.  With d = lb - la and a width w >= 0 the band is the cells with
+ * min(0, d) - w <= j - i <= max(0, d) + w.  A path that leaves it holds at least 2 (w + 1) + |d| gap
+ * columns in at least two runs and scores at most UB(w) = min(la, lb) - |d| - 3 (w + 1) - 4.  A banded
+ * score S_w (every state outside the computed region at -2^30) is certified when
+ *   (A) S_w > NINF + min(la, lb)   (no path from a finite "-infinity" boundary state reaches it), and
+ *   (B) S_w > UB(w);
+ * then S_w is the full score S, every optimal path lies in the band, and the chain of choices is
+ * the full matrix's, choice for choice.  The width a pair needs is
+ * w*(S) = max(0, floor((min(la, lb) - |d| - 4 - S) / 3)).
+ * mc_set_align_band: mode 0 (the default) keeps the full record: every call is bit for bit and byte
+ * for byte what it is without this entry, mc_nw_align_profile's choice bytes included.  Mode 1 makes
+ * mc_nw_align_strands, mc_nw_pileup_strands, mc_nw_qpileup_strands and mc_nw_msa_begin plan a width
+ * per pair first and record the band alone; their results do not change by a bit.  Any other mode
+ * is MC_ERR_ARG.  The mode stays with the context.
+ * The plan (mc_nw_band_plan is the search alone): the pairs go through a score-only form of the
+ * banded forward kernel in mc_nw_identity_strands' batches (MC_IDENT_BATCH, MC_IDENT_BYTES).  Within
+ * a batch every pair starts at w0 = 64 and the uncertified ones are launched again at twice the
+ * width, until (A) and (B) hold or the band holds the whole matrix, at most 1 + ceil(log2(longest /
+ * w0)) rounds; S is then exact and the planned width is w*(S), whatever w0 and the schedule were.
+ * A pair is planned full (w = -1: the record and the forward kernel above) when (A) fails, when
+ * either string is empty, or when the band at w* would take no fewer bytes than the full record.
+ * Banded pairs are worked in row blocks of 256 (4 rows per lane); block k sweeps the columns its
+ * rows' band cells lie in, and the record is ceil(la / 256) * (min(lb, 256 + |d| + 2 w) + 63) * 128
+ * bytes.  The trace batches are planned on these bytes, and MC_ERR_UNSUPPORTED (a pair above
+ * MC_ALIGN_SCRATCH) is decided on them, after the search and before any trace launch or output.
+ * A walk that would leave its window is MC_ERR_HIP: the certificate says there is none.
+ * Environment, read per call: MC_BAND_W0=<n> (n >= 1) replaces w0, for tests.
+ * mc_nw_band_plan: w[i] = the planned width of pair i (-1: full), score[i] = S, mc_nw_identity_raw's
+ * score.  Errors are mc_nw_identity_strands'; a pair of 2^27 bases or more is MC_ERR_UNSUPPORTED.
+ * mc_nw_band_profile (a measurement aid): out[0] = pairs planned banded, out[1] = pairs planned
+ * full, out[2] = search launches, out[3] = device ms of the search (timed as "nw"), out[4] = the sum
+ * of the planned w over the banded pairs, since the last reset.
+ */
+int mc_set_align_band(mc_ctx *ctx, int mode /* 0 or 1 */);
+int mc_nw_band_plan(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                    int32_t *w /* m */, int32_t *score /* m */);
+int mc_nw_band_profile(mc_ctx *ctx, double *out /* 5 */, int reset);
+
+/*
  * THE ALIGNMENTS of mc_nw_align_strands piled up per centre column.  The pairs, the operand rule
  * (seq1 = the read a[i], its minus-strand string where a_minus[i] != 0; seq2 = the centre b[i] as
  * written), the batching and its environment caps are mc_nw_align_strands' own; score, len and ids

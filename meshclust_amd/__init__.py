@@ -144,6 +144,11 @@ def gpu_lib():
         lib.mc_nw_msa_counts.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         lib.mc_nw_msa_counts_profile.restype = C.c_int
         lib.mc_nw_msa_counts_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        for name in ("mc_set_align_band", "mc_nw_band_plan", "mc_nw_band_profile"):
+            getattr(lib, name).restype = C.c_int
+        lib.mc_set_align_band.argtypes = [C.c_void_p, C.c_int]
+        lib.mc_nw_band_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.mc_nw_band_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _bind_steps(lib)
         _gpu = lib
     return _gpu
@@ -237,6 +242,11 @@ def host_lib():
         lib.mcl_assign_profile.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                            C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
                                            C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+        lib.mcl_assign_band.restype = C.c_int
+        lib.mcl_assign_band.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                        C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
+                                        C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                        C.c_int]
         _host = lib
     return _host
 
@@ -636,6 +646,30 @@ class Engine:
         self._ck(self.lib.mc_nw_align_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_align_profile")
         return float(out[0]), float(out[1]), float(out[2])
 
+    def set_align_band(self, mode):
+        """mc_set_align_band: 0 (the default) the full choice record, 1 the certified band for nw_align_strands,
+        nw_pileup_strands, nw_qpileup_strands and nw_msa_begin; their results do not change."""
+        self._ck(self.lib.mc_set_align_band(self.ctx, int(mode)), "mc_set_align_band")
+
+    def nw_band_plan(self, a, b, a_minus=None):
+        """mc_nw_band_plan: the width search alone -> (w, score): the planned band width of every pair
+        (-1: the full record) and its exact score."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        am = None if a_minus is None else np.ascontiguousarray(a_minus, np.uint8)
+        assert len(b) == len(a) and (am is None or len(am) == len(a))
+        w = np.zeros(len(a), np.int32)
+        sc = np.zeros(len(a), np.int32)
+        self._ck(self.lib.mc_nw_band_plan(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(len(a)), _p(w), _p(sc)), "mc_nw_band_plan")
+        return w, sc
+
+    def nw_band_profile(self, reset=False):
+        """mc_nw_band_profile -> (pairs banded, pairs full, search launches, search ms, sum of the planned w)
+        since the last reset."""
+        out = np.zeros(5)
+        self._ck(self.lib.mc_nw_band_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_band_profile")
+        return int(out[0]), int(out[1]), int(out[2]), float(out[3]), int(out[4])
+
     def nw_pileup_strands(self, a, b, a_minus, targets, table=True):
         """mc_nw_pileup_strands: nw_align_strands' alignments piled up per centre column ->
         (table[rows, 8], row_off, score, len, ids).  ``targets``: the distinct centres (every b among
@@ -799,7 +833,8 @@ class Engine:
 
 
 def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None,
-                 identity=False, min_identity=None, paf=None, consensus=None, pileup=None, quality=False, msa=None, profile=None):
+                 identity=False, min_identity=None, paf=None, consensus=None, pileup=None, quality=False, msa=None, profile=None,
+                 band=False):
     """Place the reads of the FASTA or FASTQ file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
@@ -834,13 +869,23 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     per column (mc_nw_msa_counts; one mc_nw_msa_begin shared with ``msa``) as a TSV, one line per column of every
     centre with reads: centre, column, centre_pos, slot, base, depth, A, C, G, T, N, gap, and with ``quality`` (then
     accepted beside ``profile`` alone) wA wC wG wT wN wgap; the stats gain, last, ``profile_centres``,
-    ``profile_columns`` and the ``profile`` phase."""
+    ``profile_columns`` and the ``profile`` phase.
+    ``band``: meshclust-assign's --band (mcl_assign_band; with ``paf``, ``consensus``, ``pileup``, ``msa`` or
+    ``profile``): the alignments record the certified band alone (mc_set_align_band 1 for the run); no output
+    file changes, the stats gain, last, ``band_pairs``, ``band_full``, ``band_launches`` and ``band_w_sum``."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    if profile is not None:
+    if band:
+        rc = lib.mcl_assign_band(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                 unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
+                                 hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),
+                                 paf.encode() if paf else None, consensus.encode() if consensus else None,
+                                 pileup.encode() if pileup else None, 1 if quality else 0, msa.encode() if msa else None,
+                                 profile.encode() if profile else None, 1, buf, len(buf))
+    elif profile is not None:
         rc = lib.mcl_assign_profile(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                     unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
                                     hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../host/band.hpp"
 #include "../host/pairbatch.hpp"
 #include "abi_util.hpp"
 #include "mcgpu.hpp"
@@ -47,14 +48,124 @@ void scatter_res(const std::vector<int32_t> &res, uint64_t i0, uint64_t mb, int3
   }
 }
 
+// The width search of the certified band (host/band.hpp) over the pairs of a call,
+// before its trace batches are planned: w[i] = pair i's planned width (-1: the full record),
+// score[i] = its exact score.  The pairs go through the score-only kernel in mc_nw_identity_strands'
+// batches (the pair cap, the minus-strand strings cap, the distinct minus reads reverse-complemented
+// once).  Within a batch every pair starts at w0 and the uncertified ones are launched again at twice
+// the width, until the certificate holds or the band holds the whole matrix: the score is then exact
+// and the planned width w*(score) depends on neither w0 nor the schedule.  A launch is cut where the
+// boundary rows of its pairs of more than one block would pass BAND_BND_BYTES.  Writes only to
+// buffers of the context.  Pairs of 2^27 bases or more are the caller's to refuse first.
+constexpr uint64_t BAND_W0 = 64, BAND_BND_BYTES = 256ull << 20;
+
+uint64_t band_w0() {  // MC_BAND_W0=<n>, read per call: the first width of the search (n >= 1)
+  const char *e = getenv("MC_BAND_W0");
+  const long long v = e ? atoll(e) : 0;
+  return v >= 1 ? (uint64_t)std::min<long long>(v, 1 << 27) : BAND_W0;
+}
+
+int band_search(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m, int32_t *w, int32_t *score) {
+  const uint64_t w0 = band_w0();
+  mc::PairBatcher pb(c->h_seq_off.data(), c->n, a, b, a_minus, m, batch_caps("MC_IDENT_BATCH", MC_IDENT_BATCH_PAIRS, false));
+  std::vector<uint64_t> h_off, wcur;
+  std::vector<TracePair> recs;
+  std::vector<uint64_t> todo, next;
+  std::vector<int32_t> sc;
+  auto planned = [&](uint64_t i, int64_t la, int64_t lb, int32_t S) {
+    score[i] = S;
+    w[i] = mc::band_plan(la, lb, S);
+    c->band_stat[w[i] >= 0 ? 0 : 1] += 1;
+    if (w[i] >= 0) c->band_stat[3] += w[i];
+  };
+  while (pb.next()) {
+    if (!pb.uniq.empty()) TRY(revseq_batch(c, pb.uniq.data(), (uint32_t)pb.uniq.size(), h_off));
+    todo.clear();
+    wcur.assign(pb.i1 - pb.i0, w0);
+    for (uint64_t i = pb.i0; i < pb.i1; i++) {
+      const int64_t la = (int64_t)pb.length(a[i]), lb = (int64_t)pb.length(b[i]);
+      if (la == 0)  // (nwtrace.hip: no rows; no columns: lowerGap's column 0 wins the final maximum)
+        planned(i, la, lb, lb > 0 ? (int32_t)mc::band_neg_inf(la, lb) : 0);
+      else if (lb == 0)
+        planned(i, la, lb, (int32_t)(-2 - la));
+      else
+        todo.push_back(i);
+    }
+    while (!todo.empty()) {
+      sc.resize(todo.size());
+      for (size_t at = 0, end; at < todo.size(); at = end) {
+        recs.clear();
+        uint64_t bnd = 0;
+        for (end = at; end < todo.size(); end++) {
+          const uint64_t i = todo[end], la = pb.length(a[i]), lb = pb.length(b[i]);
+          const uint64_t need = mc::band_bnd_ints(la, lb, wcur[i - pb.i0]);
+          if (end > at && (bnd + need) * 4 > BAND_BND_BYTES) break;
+          TracePair pr{};
+          pr.a_off = pb.minus(i) ? h_off[pb.slot(a[i])] : c->h_seq_off[a[i]];
+          pr.b_off = c->h_seq_off[b[i]];
+          pr.bnd_off = bnd;
+          pr.la = (uint32_t)la;
+          pr.lb = (uint32_t)lb;
+          pr.a_rc = pb.minus(i) ? 1 : 0;
+          pr.r = mc::BAND_R;
+          pr.w = (int32_t)wcur[i - pb.i0];
+          recs.push_back(pr);
+          bnd += need;
+        }
+        const size_t n = end - at;
+        TRY(ensure(c->bs_bnd, bnd * 4 + 64));
+        TRY(ensure(c->bs_score, n * 4 + 64));
+        TRY(upload(c, c->bs_pairs, recs.data(), n, c->stream));
+        TRY(launch_nwband_scores(c, (uint32_t)n, (const TracePair *)c->bs_pairs.p, (const uint8_t *)c->rc_seq.p, (int *)c->bs_bnd.p,
+                                 (int32_t *)c->bs_score.p));
+        TRY(download_parts(c, {{sc.data() + at, c->bs_score.p, n * 4}}, c->stream));
+        c->band_stat[2] += 1;
+      }
+      next.clear();
+      for (size_t k = 0; k < todo.size(); k++) {
+        const uint64_t i = todo[k];
+        const int64_t la = (int64_t)pb.length(a[i]), lb = (int64_t)pb.length(b[i]), wi = (int64_t)wcur[i - pb.i0];
+        if (mc::band_certified(la, lb, wi, sc[k]) || mc::band_is_whole(la, lb, wi)) {
+          planned(i, la, lb, sc[k]);
+        } else {
+          wcur[i - pb.i0] = (uint64_t)std::min<int64_t>(2 * wi, std::max(la, lb));
+          next.push_back(i);
+        }
+      }
+      todo.swap(next);
+    }
+  }
+  flush_timers(c);
+  return MC_OK;
+}
+
+// the plan of a call's pairs: empty with the band off (mc_set_align_band), else band_search's widths
+int align_plan(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m, std::vector<int32_t> &plan) {
+  plan.clear();
+  if (!c->align_band || m == 0) return MC_OK;
+  plan.assign(m, -1);
+  for (uint64_t i = 0; i < m; i++)  // (align_check_caps refuses the call)
+    if ((c->h_seq_off[a[i] + 1] - c->h_seq_off[a[i]]) + (c->h_seq_off[b[i] + 1] - c->h_seq_off[b[i]]) >= (1ull << 27)) return MC_OK;
+  std::vector<int32_t> score(m);
+  return band_search(c, a, b, a_minus, m, plan.data(), score.data());
+}
+
+// the choice bytes of pair i under a plan (empty: the full record)
+uint64_t planned_bytes(const std::vector<int32_t> &plan, uint64_t i, uint64_t la, uint64_t lb) {
+  return !plan.empty() && plan[i] >= 0 ? mc::band_choice_bytes(la, lb, (uint64_t)plan[i]) : nw_trace_choice_bytes(la, lb);
+}
+
 // The pairs of mc_nw_align_strands / mc_nw_pileup_strands in batches: the forward pass and the
 // traceback of every batch, then per_batch(i0, mb, res) with the batch's TRACE_RES ints per pair
 // on the host; the batch's pair records, operation words and results are still in c->tr_pairs,
 // c->tr_ops and c->tr_res, its minus-strand strings in c->rc_seq.  `who` names the caller in errors.
+// plan: align_plan's; a pair's scratch is its planned bytes, banded or full.
 int align_batches(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m,
+                  const std::vector<int32_t> &plan,
                   const std::function<int(uint64_t, uint64_t, const std::vector<int32_t> &)> &per_batch) {
   mc::PairBatcher pb(c->h_seq_off.data(), c->n, a, b, a_minus, m, batch_caps("MC_ALIGN_BATCH", MC_ALIGN_BATCH_PAIRS, true),
                      nw_trace_choice_bytes);
+  if (!plan.empty()) pb.scratch_at = [&](uint64_t i) { return planned_bytes(plan, i, pb.length(a[i]), pb.length(b[i])); };
   std::vector<uint64_t> h_off;
   std::vector<TracePair> pairs;
   std::vector<int32_t> res;
@@ -75,10 +186,12 @@ int align_batches(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t 
       pr.la = (uint32_t)la;
       pr.lb = (uint32_t)lb;
       pr.a_rc = pb.minus(i) ? 1 : 0;
-      pr.r = (uint32_t)nw_trace_rows(la);
+      pr.w = plan.empty() ? -1 : plan[i];
+      pr.r = pr.w >= 0 ? (uint32_t)mc::BAND_R : (uint32_t)nw_trace_rows(la);
       pairs.push_back(pr);
-      chb += nw_trace_choice_bytes(la, lb);
-      if (la > 64ull * pr.r) bnd += 3 * (lb + 1);
+      chb += planned_bytes(plan, i, la, lb);
+      if (pr.w >= 0) bnd += mc::band_bnd_ints(la, lb, (uint64_t)pr.w);
+      else if (la > 64ull * pr.r) bnd += 3 * (lb + 1);
       opw += la + lb;
     }
     TRY(ensure(c->tr_choice, chb + 64));
@@ -93,7 +206,7 @@ int align_batches(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t 
     int herr = 0;
     TRY(download_parts(c, {{res.data(), c->tr_res.p, mb * TRACE_RES * 4}, {&herr, c->tr_err.p, 4}}, c->stream));
     if (herr) {
-      set_error(std::string(who) + ": a traceback did not reach the matrix's edge within la + lb steps");
+      set_error(std::string(who) + ": a traceback did not reach the matrix's edge within la + lb steps, or left its band");
       return MC_ERR_HIP;
     }
     TRY(per_batch(pb.i0, mb, res));
@@ -101,15 +214,15 @@ int align_batches(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t 
   return MC_OK;
 }
 
-// before any launch, and before any output is written: a pair that alone exceeds the scratch cap
-int align_check_caps(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t *b, uint64_t m) {
+// before any trace launch, and before any output is written: a pair whose planned bytes alone exceed the scratch cap
+int align_check_caps(mc_ctx *c, const char *who, const uint32_t *a, const uint32_t *b, uint64_t m, const std::vector<int32_t> &plan) {
   const uint64_t scr_cap = env_cap("MC_ALIGN_SCRATCH", MC_ALIGN_SCRATCH_BYTES);
   auto length = [&](uint32_t id) { return c->h_seq_off[id + 1] - c->h_seq_off[id]; };
   for (uint64_t i = 0; i < m; i++) {
     const uint64_t la = length(a[i]), lb = length(b[i]);
-    if (la + lb >= (1ull << 27) || nw_trace_choice_bytes(la, lb) > scr_cap) {
+    if (la + lb >= (1ull << 27) || planned_bytes(plan, i, la, lb) > scr_cap) {
       set_error(std::string(who) + ": pair " + std::to_string(i) + " (" + std::to_string(la) + " x " + std::to_string(lb) +
-                ") needs " + std::to_string(nw_trace_choice_bytes(la, lb)) + " bytes of choices, the cap is " +
+                ") needs " + std::to_string(planned_bytes(plan, i, la, lb)) + " bytes of choices, the cap is " +
                 std::to_string(scr_cap));
       return MC_ERR_UNSUPPORTED;
     }
@@ -169,7 +282,9 @@ int pileup_call(mc_ctx *c, const std::string &who, bool weighted, const uint32_t
         return MC_ERR_ARG;
       }
   }
-  TRY(align_check_caps(c, who.c_str(), a, b, m));
+  std::vector<int32_t> plan;
+  TRY(align_plan(c, a, b, a_minus, m, plan));
+  TRY(align_check_caps(c, who.c_str(), a, b, m, plan));
   std::vector<uint64_t> toff(nt);
   row_off[0] = 0;
   for (uint32_t t = 0; t < nt; t++) {
@@ -205,7 +320,7 @@ int pileup_call(mc_ctx *c, const std::string &who, bool weighted, const uint32_t
   const char *nv = getenv("MC_PILEUP_NAIVE");  // (a measurement aid: an atomic per column; the same table)
   const bool naive = nv && atoi(nv) != 0;
   std::vector<uint64_t> rowbase, qoff;
-  TRY(align_batches(c, who.c_str(), a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
+  TRY(align_batches(c, who.c_str(), a, b, a_minus, m, plan, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
     scatter_res(res, i0, mb, score, len, ids);
     rowbase.resize(mb);
     for (uint64_t k = 0; k < mb; k++) rowbase[k] = row_off[tindex[b[i0 + k]]];
@@ -335,7 +450,9 @@ int mc_nw_msa_begin(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8
   TRY(check_ids(c, b, m));
   std::vector<uint32_t> tindex;
   TRY(index_targets(c, who, targets, nt, b, m, tindex));
-  TRY(align_check_caps(c, who.c_str(), a, b, m));
+  std::vector<int32_t> plan;
+  TRY(align_plan(c, a, b, a_minus, m, plan));
+  TRY(align_check_caps(c, who.c_str(), a, b, m, plan));
   row_off[0] = 0;
   for (uint32_t t = 0; t < nt; t++) row_off[t + 1] = row_off[t] + (c->h_seq_off[targets[t] + 1] - c->h_seq_off[targets[t]]) + 1;
   const uint64_t rows = row_off[nt];
@@ -349,7 +466,7 @@ int mc_nw_msa_begin(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8
   std::vector<uint64_t> woff(m + 1, 0), dst, rowbase;
   uint64_t total = 0;  // operation words packed so far
   TRY(grow_keep(c, c->msa_words, 64, 0));
-  TRY(align_batches(c, who.c_str(), a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
+  TRY(align_batches(c, who.c_str(), a, b, a_minus, m, plan, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
     scatter_res(res, i0, mb, score, len, ids);
     dst.resize(mb);
     rowbase.resize(mb);
@@ -680,10 +797,12 @@ int mc_nw_align_strands(mc_ctx *c, const uint32_t *a, const uint32_t *b, const u
   MCG_CHECK(hipSetDevice(c->device));
   TRY(check_ids(c, a, m));
   TRY(check_ids(c, b, m));
-  TRY(align_check_caps(c, "mc_nw_align_strands", a, b, m));
+  std::vector<int32_t> plan;
+  TRY(align_plan(c, a, b, a_minus, m, plan));
+  TRY(align_check_caps(c, "mc_nw_align_strands", a, b, m, plan));
   std::vector<uint32_t> words, nops(m);
   std::vector<uint64_t> dst;
-  TRY(align_batches(c, "mc_nw_align_strands", a, b, a_minus, m, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
+  TRY(align_batches(c, "mc_nw_align_strands", a, b, a_minus, m, plan, [&](uint64_t i0, uint64_t mb, const std::vector<int32_t> &res) {
     scatter_res(res, i0, mb, score, len, ids);
     dst.resize(mb);
     uint64_t tot = 0;
@@ -763,6 +882,47 @@ int mc_nw_align_profile(mc_ctx *c, double *out, int reset) {
   if (reset) {
     c->fam_ms[F_NW_FWD] = c->fam_ms[F_NW_TB] = c->fam_n[F_NW_FWD] = c->fam_n[F_NW_TB] = 0;
     c->tr_choice_bytes = 0;
+  }
+  return MC_OK;
+}
+
+int mc_set_align_band(mc_ctx *c, int mode) {
+  if (!c) return MC_ERR_ARG;
+  if (mode != 0 && mode != 1) {
+    set_error("mc_set_align_band: mode " + std::to_string(mode) + " (0: the full record, 1: the certified band)");
+    return MC_ERR_ARG;
+  }
+  c->align_band = mode;
+  return MC_OK;
+}
+
+int mc_nw_band_plan(mc_ctx *c, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m, int32_t *w, int32_t *score) {
+  if (!c || !c->codes.p) return MC_ERR_STATE;
+  if (m == 0) return MC_OK;
+  if (!a || !b || !w || !score) return MC_ERR_ARG;
+  MCG_CHECK(hipSetDevice(c->device));
+  TRY(check_ids(c, a, m));
+  TRY(check_ids(c, b, m));
+  for (uint64_t i = 0; i < m; i++)
+    if ((c->h_seq_off[a[i] + 1] - c->h_seq_off[a[i]]) + (c->h_seq_off[b[i] + 1] - c->h_seq_off[b[i]]) >= (1ull << 27)) {
+      set_error("mc_nw_band_plan: pair " + std::to_string(i) + " has 2^27 bases or more");
+      return MC_ERR_UNSUPPORTED;
+    }
+  return band_search(c, a, b, a_minus, m, w, score);
+}
+
+int mc_nw_band_profile(mc_ctx *c, double *out, int reset) {
+  if (!c || !out) return MC_ERR_ARG;
+  (void)hipStreamSynchronize(c->stream);
+  flush_timers(c);
+  out[0] = c->band_stat[0];
+  out[1] = c->band_stat[1];
+  out[2] = c->band_stat[2];
+  out[3] = c->fam_ms[F_NW_BAND];
+  out[4] = c->band_stat[3];
+  if (reset) {
+    c->fam_ms[F_NW_BAND] = c->fam_n[F_NW_BAND] = 0;
+    for (double &v : c->band_stat) v = 0;
   }
   return MC_OK;
 }

@@ -32,8 +32,9 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // mc_timers and are kept apart only for mc_nw_align_profile; F_NW_PU: the pile-up kernels of
 // pileup.hip, likewise part of F_NW and kept apart for mc_nw_pileup_profile; F_NW_MSAW / F_NW_MSAR:
 // the width + column kernels and the render kernel of msa.hip, part of F_NW, for mc_nw_msa_profile;
-// F_NW_MSAC: the counts kernels of msa.hip (mc_nw_msa_counts), part of F_NW, for mc_nw_msa_counts_profile
-enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NW_MSAC, F_NALL };
+// F_NW_MSAC: the counts kernels of msa.hip (mc_nw_msa_counts), part of F_NW, for mc_nw_msa_counts_profile;
+// F_NW_BAND: the score-only launches of the width search (nwband.hip), part of F_NW, for mc_nw_band_profile
+enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NW_MSAC, F_NW_BAND, F_NALL };
 
 // Classifier in the form the kernels consume (mc_classifier + the exact decision threshold).
 struct DevClassifier {
@@ -92,11 +93,29 @@ struct Buf {
 // One pair of mc_nw_align_strands' batch (nwtrace.hip): seq1 at a_off of the minus-strand buffer
 // (a_rc) or of the loaded codes, seq2 at b_off of the codes; r rows per lane; where the pair's
 // choice words (bytes), boundary row (ints) and operation words (uint32, la + lb of them) start.
+// w < 0: the full record of nwtrace.hip; w >= 0: the banded record of nwband.hip at that width
+// (host/band.hpp; r is then BAND_R).
 struct TracePair {
   uint64_t a_off, b_off, ch_off, bnd_off, ops_off;
   uint32_t la, lb, a_rc, r;
+  int32_t w = -1;
+  uint32_t pad = 0;
 };
 constexpr int TRACE_RES = 5;  // per pair: score, columns, identities, operation words, final state
+
+// what the kernels of nwtrace.hip and nwband.hip are launched with
+struct TraceArgs {
+  const uint8_t *codes;  // the loaded sequences (seq2 always, seq1 of a plus pair)
+  const uint8_t *rc;     // the batch's minus-strand strings (seq1 of a minus pair)
+  const TracePair *pairs;
+  const uint32_t *pidx;  // forward: the pairs of this launch (one R)
+  uint32_t npairs;
+  uint8_t *choice;
+  int *bnd;
+  int32_t *res;  // TRACE_RES ints per pair
+  uint32_t *ops;
+  int *err;
+};
 
 // One row of a render batch of mc_nw_msa_rows (msa.hip): W bytes at out_off of the batch's output;
 // seq1 at a_off of the minus-strand buffer (a_rc) or of the loaded codes; its nw operation words at
@@ -209,6 +228,12 @@ struct mc_ctx {
   // results, launch lists, output offsets and packed operations; the error word
   mcg::Buf tr_choice, tr_bnd, tr_ops, tr_pairs, tr_res, tr_idx, tr_dst, tr_out, tr_err;
   double tr_choice_bytes = 0;  // choice bytes written since the last mc_nw_align_profile reset
+  // mc_set_align_band: 0 the full record, 1 the certified band.  The width search's
+  // pair records, boundary rows and scores of a launch; mc_nw_band_profile's counters: pairs
+  // banded, pairs full, search launches, the sum of the planned w
+  int align_band = 0;
+  mcg::Buf bs_pairs, bs_bnd, bs_score;
+  double band_stat[4] = {0, 0, 0, 0};
   // mc_nw_pileup_strands: the call's table (8 counters per row) and its two difference arrays
   // ('=' and 'D' coverage, an int per row), a batch's row base per pair, the targets' code offsets
   // and row offsets
@@ -336,6 +361,14 @@ int launch_nw_trace(mc_ctx *c, const std::vector<TracePair> &h_pairs, const Trac
                     uint8_t *d_choice, int *d_bnd, uint32_t *d_ops, int32_t *d_res, int *d_err);
 int launch_nw_pack(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint32_t *d_ops, const int32_t *d_res,
                    const uint64_t *d_dst, uint32_t *d_out);
+
+// nwband.hip: the banded forward kernel over the pairs q.pidx[0 .. q.npairs) (every one with w >= 0;
+// called by launch_nw_trace inside its forward timer), the traceback of a batch that holds a banded
+// pair (a thread per pair, either record), and the width search's score-only launch: the banded
+// score of pair p at its w to d_score[p]
+int launch_nwband_forward(mc_ctx *c, const TraceArgs &q);
+int launch_nwband_traceback(mc_ctx *c, const TraceArgs &q);
+int launch_nwband_scores(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint8_t *d_rc, int *d_bnd, int32_t *d_score);
 
 // pileup.hip: the pairs of a batch (after launch_nw_trace) added to the call's table and
 // difference arrays, pair p's rows starting at d_rowbase[p]; naive: every column its own atomic.

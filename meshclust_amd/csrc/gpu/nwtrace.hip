@@ -39,6 +39,7 @@
 // order.  nwt_pack_kernel then copies every pair's words to their place in the call's output.
 #include <algorithm>
 
+#include "../host/band.hpp"
 #include "mcgpu.hpp"
 
 namespace mcg {
@@ -62,19 +63,6 @@ struct ChoiceWord<8> {
 template <>
 struct ChoiceWord<16> {
   using type = uint64_t;
-};
-
-struct TraceArgs {
-  const uint8_t *codes;  // the loaded sequences (seq2 always, seq1 of a plus pair)
-  const uint8_t *rc;     // the batch's minus-strand strings (seq1 of a minus pair)
-  const TracePair *pairs;
-  const uint32_t *pidx;  // forward: the pairs of this launch (one R)
-  uint32_t npairs;
-  uint8_t *choice;
-  int *bnd;
-  int32_t *res;  // TRACE_RES ints per pair
-  uint32_t *ops;
-  int *err;
 };
 
 __device__ __forceinline__ int neg_inf(int la, int lb) {  // GlobAlignE.cpp:125-135
@@ -344,25 +332,23 @@ __global__ __launch_bounds__(64) void nwt_pack_kernel(TraceArgs q, const uint64_
 
 }  // namespace
 
-int nw_trace_rows(uint64_t la) { return la <= 256 ? 4 : la <= 512 ? 8 : 16; }
+int nw_trace_rows(uint64_t la) { return mc::full_rows_per_lane(la); }
 
-uint64_t nw_trace_choice_bytes(uint64_t la, uint64_t lb) {
-  const uint64_t R = (uint64_t)nw_trace_rows(la);
-  return (la + 64 * R - 1) / (64 * R) * (lb + 63) * 32 * R;
-}
+uint64_t nw_trace_choice_bytes(uint64_t la, uint64_t lb) { return mc::full_choice_bytes(la, lb); }
 
 int launch_nw_trace(mc_ctx *c, const std::vector<TracePair> &h_pairs, const TracePair *d_pairs, const uint8_t *d_rc,
                     uint8_t *d_choice, int *d_bnd, uint32_t *d_ops, int32_t *d_res, int *d_err) {
   const size_t m = h_pairs.size();
   if (m == 0) return MC_OK;
-  std::vector<uint32_t> bucket[3];  // R = 4, 8, 16
-  for (size_t i = 0; i < m; i++) bucket[h_pairs[i].r == 4 ? 0 : h_pairs[i].r == 8 ? 1 : 2].push_back((uint32_t)i);
+  std::vector<uint32_t> bucket[4];  // R = 4, 8, 16; the banded pairs (nwband.hip)
+  for (size_t i = 0; i < m; i++)
+    bucket[h_pairs[i].w >= 0 ? 3 : h_pairs[i].r == 4 ? 0 : h_pairs[i].r == 8 ? 1 : 2].push_back((uint32_t)i);
   if (ensure(c->tr_idx, m * 4 + 16)) return MC_ERR_OOM;
   TraceArgs q{(const uint8_t *)c->codes.p, d_rc, d_pairs, nullptr, 0, d_choice, d_bnd, d_res, d_ops, d_err};
   MCG_CHECK(hipMemsetAsync(d_err, 0, 4, c->stream));
   timed_begin(c);
   size_t io = 0;
-  for (int k = 0; k < 3; k++) {
+  for (int k = 0; k < 4; k++) {
     if (bucket[k].empty()) continue;
     uint32_t *d_idx = (uint32_t *)c->tr_idx.p + io;
     if (int rc = stage_h2d(c, d_idx, bucket[k].data(), bucket[k].size() * 4)) return rc;
@@ -370,7 +356,8 @@ int launch_nw_trace(mc_ctx *c, const std::vector<TracePair> &h_pairs, const Trac
     q.npairs = (uint32_t)bucket[k].size();
     if (k == 0) nwt_forward_kernel<4><<<q.npairs, 64, 0, c->stream>>>(q);
     else if (k == 1) nwt_forward_kernel<8><<<q.npairs, 64, 0, c->stream>>>(q);
-    else nwt_forward_kernel<16><<<q.npairs, 64, 0, c->stream>>>(q);
+    else if (k == 2) nwt_forward_kernel<16><<<q.npairs, 64, 0, c->stream>>>(q);
+    else if (int rc = launch_nwband_forward(c, q)) return rc;
     MCG_CHECK(hipGetLastError());
     io += bucket[k].size();
   }
@@ -378,7 +365,8 @@ int launch_nw_trace(mc_ctx *c, const std::vector<TracePair> &h_pairs, const Trac
   q.pidx = nullptr;
   q.npairs = (uint32_t)m;
   timed_begin(c);
-  nwt_traceback_kernel<<<(unsigned)((m + 63) / 64), 64, 0, c->stream>>>(q);
+  if (bucket[3].empty()) nwt_traceback_kernel<<<(unsigned)((m + 63) / 64), 64, 0, c->stream>>>(q);
+  else if (int rc = launch_nwband_traceback(c, q)) return rc;  // (a batch with a banded pair: the walk that knows both records)
   MCG_CHECK(hipGetLastError());
   timed_end(c, F_NW_TB);
   return MC_OK;

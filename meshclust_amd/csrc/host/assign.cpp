@@ -27,7 +27,7 @@ namespace mc {
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
     "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--consensus FILE] "
-    "[--pileup FILE] [--quality] [--msa FILE] [--profile FILE] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
+    "[--pileup FILE] [--quality] [--msa FILE] [--profile FILE] [--band] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
     "                  (implied by a version-2 model, saved by meshclust --both-strands: reads and centres are then\n"
     "                  scored once on their canonical rows and every hit's strand comes from mc_orient_pairs; with\n"
@@ -56,6 +56,8 @@ static const char *kUsage =
     "  --profile FILE  (implies --identity) that alignment counted per column, for centres with reads: centre, column,\n"
     "                  centre_pos, slot (0: a centre base; from 1: an inserted column before it), base (- inserted),\n"
     "                  depth, A, C, G, T, N, gap; with --quality (FASTQ reads) also wA wC wG wT wN wgap\n"
+    "  --band          (with --paf, --consensus, --pileup, --msa or --profile) record only a certified band of every\n"
+    "                  alignment's choices (mc_set_align_band): less scratch, more pairs per batch, no output file changes\n"
     "  reads and centres may be FASTA or FASTQ files (decided per file); without --quality the qualities are skipped\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
@@ -98,6 +100,8 @@ AssignOptions parse_assign_options(int argc, char **argv) {
       o.identity = true;
     } else if (arg == "--quality") {
       o.quality = true;
+    } else if (arg == "--band") {
+      o.band = true;
     } else if (arg == "--msa" && has) {
       o.msa = argv[++i];
       o.identity = true;
@@ -115,6 +119,8 @@ AssignOptions parse_assign_options(int argc, char **argv) {
   if ((o.top > 0) != !o.hits.empty()) throw Error(std::string("--top K and --hits FILE are given together\n") + kUsage, 1);
   if (o.quality && o.consensus.empty() && o.pileup.empty() && o.profile.empty())
     throw Error(std::string("--quality needs --consensus FILE and/or --pileup FILE (or --profile FILE)\n") + kUsage, 1);
+  if (o.band && o.paf.empty() && o.consensus.empty() && o.pileup.empty() && o.msa.empty() && o.profile.empty())
+    throw Error(std::string("--band needs --paf, --consensus, --pileup, --msa or --profile\n") + kUsage, 1);
   return o;
 }
 
@@ -553,6 +559,18 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
     check(mc_ctx_create(opt.device, &own.c), "mc_ctx_create");
     ctx = own.c;
   }
+  struct BandOff {  // --band: the certified band for this run's alignments, the context left at the full record
+    mc_ctx *c = nullptr;
+    ~BandOff() {
+      if (c) mc_set_align_band(c, 0);
+    }
+  } band_off;
+  if (opt.band) {
+    double unused[5];
+    check(mc_set_align_band(ctx, 1), "mc_set_align_band");
+    band_off.c = ctx;
+    check(mc_nw_band_profile(ctx, unused, 1), "mc_nw_band_profile");
+  }
   t0 = std::chrono::steady_clock::now();
   check(mc_load_packed(ctx, ds.packed.data(), ds.pk_off.data(), ds.seq_off.data(), ds.size(), ds.exc_pos.data(),
                        ds.exc_val.data(), ds.exc_pos.size(), ds.seg.data(), ds.seg_off.data()),
@@ -859,12 +877,21 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
     if (fclose(h) != 0 || !hok) throw Error("cannot write " + opt.hits, 1);
   }
   r.write_ms = ms_since(t0);
+  if (opt.band) {
+    double bp[5];
+    check(mc_nw_band_profile(ctx, bp, 0), "mc_nw_band_profile");
+    r.band = true;
+    r.band_pairs = (uint64_t)bp[0];
+    r.band_full = (uint64_t)bp[1];
+    r.band_launches = (uint64_t)bp[2];
+    r.band_w_sum = (uint64_t)bp[4];
+  }
   return r;
 }
 
 std::string assign_stats_json(const AssignResult &r) {
   // (one strand, no --top, no --identity: exactly the keys there were before any of the options)
-  char b[1920], s[704] = "", idms[48] = "", msa[224] = "", msams[48] = "", prof[128] = "", profms[48] = "";
+  char b[2176], s[704] = "", idms[48] = "", msa[224] = "", msams[48] = "", prof[128] = "", profms[48] = "", band[224] = "";
   int n = 0;
   if (r.strands != MC_STRAND_PLUS)
     n = snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
@@ -894,14 +921,18 @@ std::string assign_stats_json(const AssignResult &r) {
              (unsigned long long)r.profile_columns);
     snprintf(profms, sizeof profms, ", \"profile\": %.3f", r.profile_ms);
   }
+  if (r.band)  // after every key there was before --band
+    snprintf(band, sizeof band, ", \"band_pairs\": %llu, \"band_full\": %llu, \"band_launches\": %llu, \"band_w_sum\": %llu",
+             (unsigned long long)r.band_pairs, (unsigned long long)r.band_full, (unsigned long long)r.band_launches,
+             (unsigned long long)r.band_w_sum);
   snprintf(b, sizeof b,
            "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, %s\"k\": %d, \"width\": %d, "
            "\"path\": \"%s\", \"candidate_pairs\": %llu, \"fallback_pairs\": %llu, \"device_us\": %llu, "
-           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f%s%s}%s%s}",
+           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f%s%s}%s%s%s}",
            (unsigned long long)r.reads, (unsigned long long)r.centres, (unsigned long long)r.assigned,
            (unsigned long long)(r.reads - r.assigned), s, r.k, r.width, r.path.c_str(), (unsigned long long)r.candidates,
            (unsigned long long)r.fallbacks, (unsigned long long)r.device_us, r.parse_ms, r.upload_ms, r.kmer_ms,
-           r.assign_ms, idms, r.write_ms, msams, profms, msa, prof);
+           r.assign_ms, idms, r.write_ms, msams, profms, msa, prof, band);
   return b;
 }
 

@@ -25,6 +25,7 @@ struct AssignOptions {
   bool quality = false;       // --quality (with consensus and/or pileup; FASTQ reads): the pile-up weighed by base quality
   std::string msa;            // --msa FILE (implies identity): every centre's reads laid out in common columns, aligned FASTA
   std::string profile;        // --profile FILE (implies identity): the column profile of every centre's alignment, TSV
+  bool band = false;          // --band (with paf, consensus, pileup, msa or profile): the certified band for the alignments
 };
 
 struct AssignResult {
@@ -50,6 +51,8 @@ struct AssignResult {
   uint64_t msa_pairs = 0, msa_centres = 0, msa_columns = 0, msa_bytes = 0;
   bool profile = false;          // --profile: centres with a read, the columns written
   uint64_t profile_centres = 0, profile_columns = 0;
+  bool band = false;             // --band: pairs planned banded and full, search launches, the sum of the planned widths
+  uint64_t band_pairs = 0, band_full = 0, band_launches = 0, band_w_sum = 0;
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
   double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0, msa_ms = 0, profile_ms = 0;
 };
@@ -114,6 +117,10 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // r + 1 (L + 1 after the last base), slot t + 1 and base '-'.  With quality (then also accepted
 // beside profile alone) every line gains wA wC wG wT wN wgap.  The stats gain, after every other
 // key, "profile_centres" and "profile_columns", and the phases "profile".
+// With band (it needs paf, consensus, pileup, msa or profile: parse_assign_options, usage error) the context is
+// set to mc_set_align_band 1 for the run and back to 0 at its end: every alignment pass plans a width per pair
+// and records the certified band alone.  No output file changes.  The stats gain, after every other key,
+// "band_pairs", "band_full", "band_launches" and "band_w_sum" (mc_nw_band_profile over the run).
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt);
 std::string assign_stats_json(const AssignResult &r);
 int assign_main(int argc, char **argv);

@@ -17,10 +17,11 @@ extern "C" {
 static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
                         int threads, const char *tsv, const char *unassigned, bool both_strands, int top, const char *hits,
                         int identity, double min_identity, const char *paf, const char *consensus, const char *pileup,
-                        bool quality, const char *msa, const char *profile, char *stats, int cap) {
+                        bool quality, const char *msa, const char *profile, bool band, char *stats, int cap) {
   try {
     mc::AssignOptions opt;
     opt.quality = quality;
+    opt.band = band;
     if (msa) opt.msa = msa;
     if (profile) opt.profile = profile;
     if (paf) opt.paf = paf;
@@ -44,6 +45,8 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
     if (opt.model.empty() || opt.centres.empty() || opt.reads.empty()) throw mc::Error("mcl_assign: model, centres and reads are required", 1);
     if (quality && opt.consensus.empty() && opt.pileup.empty() && opt.profile.empty())
       throw mc::Error("mcl_assign_qconsensus: quality needs consensus and/or pileup (or profile)", 1);
+    if (band && opt.paf.empty() && opt.consensus.empty() && opt.pileup.empty() && opt.msa.empty() && opt.profile.empty())
+      throw mc::Error("mcl_assign_band: band needs paf, consensus, pileup, msa or profile", 1);
     const mc::AssignResult r = mc::run_assign(ctx, opt);
     if (stats && cap > 0) snprintf(stats, cap, "%s", mc::assign_stats_json(r).c_str());
     return 0;
@@ -61,7 +64,7 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
 
 int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
                const char *tsv, const char *unassigned, char *stats, int cap) {
-  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, false, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, false, nullptr, nullptr, stats, cap);
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, false, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, false, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign with meshclust-assign's --both-strands when both_strands is non-zero (mc_assign_strands
@@ -69,7 +72,7 @@ int mcl_assign(mc_ctx *ctx, const char *model, const char *centres, const char *
 // Where only the pair list applies it returns 2 with the reason in stats.
 int mcl_assign_strands(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
                        int threads, const char *tsv, const char *unassigned, int both_strands, char *stats, int cap) {
-  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, false, nullptr, nullptr, stats, cap);
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, 0, nullptr, 0, -1.0, nullptr, nullptr, nullptr, false, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign_strands with meshclust-assign's --top `top` --hits `hits` (mc_assign_top): the TSV is
@@ -79,7 +82,7 @@ int mcl_assign_top(mc_ctx *ctx, const char *model, const char *centres, const ch
                    const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, char *stats,
                    int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, 0, -1.0, nullptr, nullptr,
-                      nullptr, false, nullptr, nullptr, stats, cap);
+                      nullptr, false, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign_top with meshclust-assign's --identity (identity non-zero) and --min-identity
@@ -90,7 +93,7 @@ int mcl_assign_identity(mc_ctx *ctx, const char *model, const char *centres, con
                         const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
                         double min_identity, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, nullptr, nullptr, nullptr, false, nullptr, nullptr, stats, cap);
+                      min_identity, nullptr, nullptr, nullptr, false, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign_identity with meshclust-assign's --paf `paf` (mc_nw_align_strands; implies identity):
@@ -100,7 +103,7 @@ int mcl_assign_paf(mc_ctx *ctx, const char *model, const char *centres, const ch
                    const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
                    double min_identity, const char *paf, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, paf, nullptr, nullptr, false, nullptr, nullptr, stats, cap);
+                      min_identity, paf, nullptr, nullptr, false, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign_paf with meshclust-assign's --consensus `consensus` and --pileup `pileup`
@@ -112,7 +115,7 @@ int mcl_assign_consensus(mc_ctx *ctx, const char *model, const char *centres, co
                          const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
                          double min_identity, const char *paf, const char *consensus, const char *pileup, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, paf, consensus, pileup, false, nullptr, nullptr, stats, cap);
+                      min_identity, paf, consensus, pileup, false, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign_consensus with meshclust-assign's --quality when quality is non-zero (mc_load_qualities,
@@ -124,7 +127,7 @@ int mcl_assign_qconsensus(mc_ctx *ctx, const char *model, const char *centres, c
                           double min_identity, const char *paf, const char *consensus, const char *pileup, int quality,
                           char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, paf, consensus, pileup, quality != 0, nullptr, nullptr, stats, cap);
+                      min_identity, paf, consensus, pileup, quality != 0, nullptr, nullptr, false, stats, cap);
 }
 
 // mcl_assign_qconsensus with meshclust-assign's --msa `msa` (mc_nw_msa_begin / mc_nw_msa_rows; implies
@@ -136,7 +139,7 @@ int mcl_assign_msa(mc_ctx *ctx, const char *model, const char *centres, const ch
                    double min_identity, const char *paf, const char *consensus, const char *pileup, int quality, const char *msa,
                    char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, paf, consensus, pileup, quality != 0, msa, nullptr, stats, cap);
+                      min_identity, paf, consensus, pileup, quality != 0, msa, nullptr, false, stats, cap);
 }
 
 // mcl_assign_msa with meshclust-assign's --profile `profile` (mc_nw_msa_counts over the plan --msa
@@ -149,7 +152,19 @@ int mcl_assign_profile(mc_ctx *ctx, const char *model, const char *centres, cons
                        double min_identity, const char *paf, const char *consensus, const char *pileup, int quality, const char *msa,
                        const char *profile, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
-                      min_identity, paf, consensus, pileup, quality != 0, msa, profile, stats, cap);
+                      min_identity, paf, consensus, pileup, quality != 0, msa, profile, false, stats, cap);
+}
+
+// mcl_assign_profile with meshclust-assign's --band when band is non-zero (mc_set_align_band 1 for the run, 0
+// again at its end): it needs paf, consensus, pileup, msa or profile; every alignment records the certified
+// band alone, no output file changes, the summary gains, after every other key, "band_pairs", "band_full",
+// "band_launches" and "band_w_sum".  band = 0 is mcl_assign_profile.
+int mcl_assign_band(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
+                    const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
+                    double min_identity, const char *paf, const char *consensus, const char *pileup, int quality, const char *msa,
+                    const char *profile, int band, char *stats, int cap) {
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
+                      min_identity, paf, consensus, pileup, quality != 0, msa, profile, band != 0, stats, cap);
 }
 
 // Records ids[0..n) of a parsed dataset (mcl_parse) as FASTA: header lines unchanged, each
