@@ -635,6 +635,48 @@ int mc_nw_msa_counts(mc_ctx *ctx, uint32_t first_target, uint32_t ntargets, uint
 int mc_nw_msa_counts_profile(mc_ctx *ctx, double *out /* 1 */, int reset);
 
 /*
+ * THE ALLELES AT CHOSEN COLUMNS of the multiple alignment: what every read carries at the few columns
+ * where its cluster disagrees with itself, so that S bytes per pair come back instead of its whole
+ * row.  mc_nw_msa_sites works on the plan of the last mc_nw_msa_begin; nt and m are the plan's.
+ * Target t owns the sites sites[site_off[t] .. site_off[t + 1]), S_t columns of its block: strictly
+ * ascending, each < W_t; S_t may be 0 and may be W_t.  Pairs are numbered as mc_nw_msa_rows numbers
+ * them: pair i is row nt + i, in the list order of begin.  For pairs first .. first + count, with
+ * t(i) the target of pair i:
+ *   off (count + 1, required)   the prefix sums of S_t(i)
+ *   alleles[off[k] + s]         byte sites[site_off[t] + s] of the row mc_nw_msa_rows renders for pair
+ *                               first + k: that row restricted to the chosen columns, byte for byte,
+ *                               MC_MSA_GAP included
+ *   quals[off[k] + s]           (may be NULL) the weight pair first + k adds to that column of
+ *                               mc_nw_msa_counts' wcounts: where the column holds a base of the pair
+ *                               ('=', 'X', or an inserted base in its slot) Qs of that base as aligned;
+ *                               at a centre column the pair deletes mc_nw_qpileup_strands' 'D' rule
+ *                               (the smaller quality around the gap); in a slot the pair leaves
+ *                               empty 0
+ * The bytes depend neither on batching nor on the split of the pairs over calls.  The plan is
+ * unchanged: the entry may be mixed freely with rows, counts and the other alignment entries.
+ * No plan: MC_ERR_STATE.  A range past m, a site_off that does not start at 0 or decreases, a site
+ * list that is not strictly ascending within a target or holds a site >= W_t: MC_ERR_ARG.  alleles
+ * NULL: the offsets only, no device work; quals non-NULL with alleles NULL: MC_ERR_ARG.  quals non-NULL
+ * with no qualities loaded: MC_ERR_STATE.  alleles non-NULL with cap < off[count]: MC_ERR_ARG, off
+ * valid, nothing else written.  count = 0: MC_OK.  All of these are found before any launch, and
+ * nothing is written except where said.
+ * Device: for the targets the requested pairs have, a lane per site finds its (row, slot) in the target's
+ * columns by bisection, into a context-owned buffer kept for the call (every list is validated, only the
+ * span of the site list those targets cover is uploaded).  The pairs go in batches whose outputs stay within
+ * MC_MSA_BATCH_BYTES (MC_MSA_BYTES lowers it) and whose minus-strand strings are batched as
+ * mc_nw_msa_rows' (MC_IDENT_BYTES, the distinct minus reads of a batch reverse-complemented once).
+ * A batch's alleles are filled with the gap and its weights with 0; a wavefront per pair then walks the
+ * plan's operation words, and the lane that owns a run stores the bytes of the sites inside it: every
+ * non-gap byte is stored exactly once.  Nothing is aligned again.  Timed as "nw", the reverse
+ * complement as "layout".  mc_nw_msa_sites_profile: out[0] = device ms of these kernels since the last
+ * reset; mc_nw_msa_profile's and mc_nw_msa_counts_profile's values do not include them.
+ */
+int mc_nw_msa_sites(mc_ctx *ctx, const uint64_t *site_off /* nt + 1 */, const uint32_t *sites /* site_off[nt] */,
+                    uint64_t first, uint64_t count, uint8_t *alleles, uint8_t *quals /* may be NULL */, uint64_t cap,
+                    uint64_t *off /* count + 1, required */);
+int mc_nw_msa_sites_profile(mc_ctx *ctx, double *out /* 1 */, int reset);
+
+/*
  * Accumulation (ClusterFactory::accumulate, ClusterFactory.cpp:637-714).
  * The bvec of Runner.cpp:342-350 is only ever shrunk after insert_finalize, so the device
  * holds one static candidate order (bin-major, length-sorted within bins) plus an alive

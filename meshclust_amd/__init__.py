@@ -144,6 +144,11 @@ def gpu_lib():
         lib.mc_nw_msa_counts.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         lib.mc_nw_msa_counts_profile.restype = C.c_int
         lib.mc_nw_msa_counts_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.mc_nw_msa_sites.restype = C.c_int
+        lib.mc_nw_msa_sites.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.c_void_p]
+        lib.mc_nw_msa_sites_profile.restype = C.c_int
+        lib.mc_nw_msa_sites_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         for name in ("mc_set_align_band", "mc_nw_band_plan", "mc_nw_band_profile"):
             getattr(lib, name).restype = C.c_int
         lib.mc_set_align_band.argtypes = [C.c_void_p, C.c_int]
@@ -247,6 +252,9 @@ def host_lib():
                                         C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double,
                                         C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
                                         C.c_int]
+        lib.mcl_assign_variants.restype = C.c_int
+        lib.mcl_assign_variants.argtypes = lib.mcl_assign_band.argtypes[:-2] + [C.c_char_p, C.c_char_p, C.c_char_p, C.c_double,
+                                                                                C.c_longlong, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -808,6 +816,33 @@ class Engine:
         self._ck(self.lib.mc_nw_msa_counts_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_msa_counts_profile")
         return float(out[0])
 
+    def nw_msa_sites(self, site_off, sites, first, count, quals=False, alleles=True):
+        """mc_nw_msa_sites: what pairs first .. first + count of the plan carry at chosen columns of
+        their targets' blocks -> (off, alleles) or, with ``quals`` (qualities loaded), (off, alleles,
+        quals).  Target t's sites are sites[site_off[t] .. site_off[t + 1]), strictly ascending
+        columns of its block; pair k's bytes are alleles[off[k] .. off[k + 1]): its nw_msa_rows row at
+        those columns, gaps MSA_GAP.  quals: the weight the pair adds to that column of nw_msa_counts'
+        wcounts.  ``alleles=False``: (off,) only, no device work."""
+        so = np.ascontiguousarray(site_off, np.uint64)
+        st = np.ascontiguousarray(sites, np.uint32)
+        off = np.zeros(count + 1, np.uint64)
+        self._ck(self.lib.mc_nw_msa_sites(self.ctx, _p(so), _p(st), C.c_uint64(first), C.c_uint64(count), None, None, C.c_uint64(0),
+                                        _p(off)), "mc_nw_msa_sites")
+        if not alleles:
+            return (off,)
+        n = int(off[-1])
+        al = np.zeros(n, np.uint8)
+        ql = np.zeros(n, np.uint8) if quals else None
+        self._ck(self.lib.mc_nw_msa_sites(self.ctx, _p(so), _p(st), C.c_uint64(first), C.c_uint64(count), _p(al), _p(ql), C.c_uint64(n),
+                                        _p(off)), "mc_nw_msa_sites")
+        return (off, al, ql) if quals else (off, al)
+
+    def nw_msa_sites_profile(self, reset=False):
+        """mc_nw_msa_sites_profile -> device ms of nw_msa_sites' kernels since the last reset."""
+        out = np.zeros(1)
+        self._ck(self.lib.mc_nw_msa_sites_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_msa_sites_profile")
+        return float(out[0])
+
     def nw_identity_raw(self, a_cat, a_off, b_cat, b_off):
         a_cat = np.ascontiguousarray(a_cat, np.uint8)
         b_cat = np.ascontiguousarray(b_cat, np.uint8)
@@ -834,7 +869,7 @@ class Engine:
 
 def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None,
                  identity=False, min_identity=None, paf=None, consensus=None, pileup=None, quality=False, msa=None, profile=None,
-                 band=False):
+                 band=False, variants=None, alleles=None, haplotypes=None, min_allele_frac=0.2, min_allele_count=2):
     """Place the reads of the FASTA or FASTQ file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
@@ -872,13 +907,28 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     ``profile_columns`` and the ``profile`` phase.
     ``band``: meshclust-assign's --band (mcl_assign_band; with ``paf``, ``consensus``, ``pileup``, ``msa`` or
     ``profile``): the alignments record the certified band alone (mc_set_align_band 1 for the run); no output
-    file changes, the stats gain, last, ``band_pairs``, ``band_full``, ``band_launches`` and ``band_w_sum``."""
+    file changes, the stats gain, last, ``band_pairs``, ``band_full``, ``band_launches`` and ``band_w_sum``.
+    ``variants`` / ``alleles`` / ``haplotypes``: meshclust-assign's --variants FILE, --alleles FILE and --haplotypes FILE
+    (mcl_assign_variants; each implies ``identity``; they share ``msa``'s and ``profile``'s mc_nw_msa_begin): the
+    ``profile`` lines of every centre's variant sites -- the columns whose second most frequent allele (A, C, G, T or
+    gap) is seen ``min_allele_count`` times or more and in ``min_allele_frac`` of the rows or more --, one line per
+    assigned read with its characters at its centre's sites (mc_nw_msa_sites; with ``quality`` their weights too),
+    and per centre with a site its distinct allele strings: centre, rank, count, depth, alleles.  ``quality`` and
+    ``band`` are accepted beside any of the three.  The stats gain, last, ``variant_centres``, ``variant_sites``,
+    ``allele_bytes`` and the ``variants`` phase."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
-    if band:
+    enc = lambda x: x.encode() if x else None
+    if variants is not None or alleles is not None or haplotypes is not None:
+        rc = lib.mcl_assign_variants(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                     enc(unassigned), 1 if both_strands else 0, int(top or 0), enc(hits), 1,
+                                     -1.0 if min_identity is None else float(min_identity), enc(paf), enc(consensus), enc(pileup),
+                                     1 if quality else 0, enc(msa), enc(profile), 1 if band else 0, enc(variants), enc(alleles),
+                                     enc(haplotypes), float(min_allele_frac), int(min_allele_count), buf, len(buf))
+    elif band:
         rc = lib.mcl_assign_band(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                  unassigned.encode() if unassigned else None, 1 if both_strands else 0, int(top or 0),
                                  hits.encode() if hits else None, 1, -1.0 if min_identity is None else float(min_identity),

@@ -677,13 +677,150 @@ int mc_nw_msa_counts_profile(mc_ctx *c, double *out, int reset) {
   return MC_OK;
 }
 
+int mc_nw_msa_sites(mc_ctx *c, const uint64_t *site_off, const uint32_t *sites, uint64_t first, uint64_t count, uint8_t *alleles,
+                    uint8_t *quals, uint64_t cap, uint64_t *off) {
+  if (!c || !c->codes.p || !c->msa_on) return MC_ERR_STATE;
+  const std::string who = "mc_nw_msa_sites";
+  if (!off || !site_off) return MC_ERR_ARG;
+  const uint64_t nt = c->msa_targets.size(), m = c->msa_a.size();
+  if (first > m || count > m - first) {
+    set_error(who + ": pairs " + std::to_string(first) + " .. " + std::to_string(first) + " + " + std::to_string(count) +
+              ", the plan has " + std::to_string(m));
+    return MC_ERR_ARG;
+  }
+  if (site_off[0] != 0) {
+    set_error(who + ": site_off starts at " + std::to_string(site_off[0]) + ", not at 0");
+    return MC_ERR_ARG;
+  }
+  for (uint64_t t = 0; t < nt; t++)
+    if (site_off[t + 1] < site_off[t]) {
+      set_error(who + ": site_off decreases at target " + std::to_string(c->msa_targets[t]));
+      return MC_ERR_ARG;
+    }
+  const uint64_t nsites = site_off[nt];
+  if (nsites && !sites) return MC_ERR_ARG;
+  for (uint64_t t = 0; t < nt; t++)
+    for (uint64_t s = site_off[t]; s < site_off[t + 1]; s++)
+      if (sites[s] >= c->msa_W[t] || (s > site_off[t] && sites[s] <= sites[s - 1])) {
+        set_error(who + ": site " + std::to_string(s - site_off[t]) + " of target " + std::to_string(c->msa_targets[t]) + ", column " +
+                  std::to_string(sites[s]) + ": the sites of a target ascend strictly and stay below its " +
+                  std::to_string(c->msa_W[t]) + " columns");
+        return MC_ERR_ARG;
+      }
+  if (quals && !alleles) {
+    set_error(who + ": quals is given with alleles (both NULL: the offsets only)");
+    return MC_ERR_ARG;
+  }
+  if (quals && !c->has_qual) {
+    set_error(who + ": no qualities are loaded (mc_load_qualities)");
+    return MC_ERR_STATE;
+  }
+  auto nsite = [&](uint64_t p) { return site_off[c->msa_tof[p] + 1] - site_off[c->msa_tof[p]]; };  // S of pair p's target
+  off[0] = 0;
+  for (uint64_t k = 0; k < count; k++) off[k + 1] = off[k] + nsite(first + k);
+  if (!alleles || count == 0) return MC_OK;
+  if (cap < off[count]) {
+    set_error(who + ": alleles holds " + std::to_string(cap) + " bytes, the pairs have " + std::to_string(off[count]));
+    return MC_ERR_ARG;
+  }
+  if (off[count] == 0) return MC_OK;
+  MCG_CHECK(hipSetDevice(c->device));
+  // the sites of the targets these pairs have and what they resolve to: kept on the device for all of the
+  // call's batches.  Only the span of the site list that those targets cover is uploaded, [lo, hi) -- for pairs
+  // sorted by target, as the assignment tool's are, no more than they need; the device offsets count from lo.
+  std::vector<uint8_t> used(nt, 0);
+  for (uint64_t k = 0; k < count; k++) used[c->msa_tof[first + k]] = 1;
+  std::vector<MsaSiteTarget> tgts;
+  uint64_t lo = nsites, hi = 0;
+  for (uint64_t t = 0; t < nt; t++)
+    if (used[t] && site_off[t + 1] > site_off[t]) {
+      lo = std::min(lo, site_off[t]);
+      hi = std::max(hi, site_off[t + 1]);
+    }
+  for (uint64_t t = 0; t < nt; t++)
+    if (used[t] && site_off[t + 1] > site_off[t])
+      tgts.push_back({c->msa_row_off[t], site_off[t] - lo, (uint32_t)(c->msa_row_off[t + 1] - c->msa_row_off[t] - 1),
+                      (uint32_t)(site_off[t + 1] - site_off[t])});
+  TRY(upload(c, c->msa_scol, sites + lo, hi - lo, c->stream));
+  TRY(upload(c, c->msa_stgt, tgts.data(), tgts.size(), c->stream));
+  TRY(ensure(c->msa_sres, (hi - lo) * sizeof(uint2) + 64));
+  TRY(launch_msa_sites_resolve(c, (uint32_t)tgts.size(), (const MsaSiteTarget *)c->msa_stgt.p, (const uint32_t *)c->msa_width.p,
+                               (const uint32_t *)c->msa_col.p, (const uint32_t *)c->msa_scol.p, (uint2 *)c->msa_sres.p));
+  const uint32_t *ids = c->msa_a.data() + first;
+  const uint8_t *minus = c->msa_minus.empty() ? nullptr : c->msa_minus.data() + first;
+  const uint64_t per = quals ? 2 : 1;  // output bytes per site
+  mc::PairBatcher pb(c->h_seq_off.data(), c->n, ids, nullptr, minus, count,
+                     {MC_IDENT_BATCH_PAIRS, env_cap("MC_IDENT_BYTES", MC_IDENT_BATCH_BYTES), env_cap("MC_MSA_BYTES", MC_MSA_BATCH_BYTES)});
+  pb.scratch_at = [&](uint64_t i) { return per * nsite(first + i); };
+  std::vector<uint64_t> h_off;
+  std::vector<MsaSitePair> recs;
+  auto fetch = [&](uint8_t *dst, const void *d, uint64_t bytes) {  // through the pinned landing buffer while it stays small
+    uint8_t *h = nullptr;
+    if (bytes <= (64ull << 20)) TRY(download_pinned(c, d, bytes, c->stream, &h));
+    if (h) {
+      memcpy(dst, h, bytes);
+    } else {
+      MCG_CHECK(hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, c->stream));
+      MCG_CHECK(hipStreamSynchronize(c->stream));
+    }
+    return (int)MC_OK;
+  };
+  while (pb.next()) {
+    const uint64_t bytes = off[pb.i1] - off[pb.i0];
+    if (bytes == 0) continue;
+    if (!pb.uniq.empty()) TRY(revseq_batch(c, pb.uniq.data(), (uint32_t)pb.uniq.size(), h_off));
+    recs.clear();
+    for (uint64_t i = pb.i0; i < pb.i1; i++) {
+      const uint64_t p = first + i, t = c->msa_tof[p];
+      MsaSitePair r{};
+      r.a_off = pb.minus(i) ? h_off[pb.slot(ids[i])] : c->h_seq_off[ids[i]];
+      r.w_off = c->msa_woff[p];
+      r.row0 = c->msa_row_off[t];
+      r.s_off = nsite(p) ? site_off[t] - lo : 0;
+      r.out_off = off[i] - off[pb.i0];
+      r.q_off = c->h_seq_off[ids[i]];
+      r.la = (uint32_t)pb.length(ids[i]);
+      r.lb = (uint32_t)(c->msa_row_off[t + 1] - r.row0 - 1);
+      r.nw = c->msa_nops[p];
+      r.S = (uint32_t)nsite(p);
+      r.a_rc = pb.minus(i) ? 1 : 0;
+      recs.push_back(r);
+    }
+    TRY(ensure(c->msa_sout, bytes + 64));
+    MCG_CHECK(hipMemsetAsync(c->msa_sout.p, MC_MSA_GAP, bytes, c->stream));
+    if (quals) {
+      TRY(ensure(c->msa_sq, bytes + 64));
+      MCG_CHECK(hipMemsetAsync(c->msa_sq.p, 0, bytes, c->stream));
+    }
+    TRY(upload(c, c->msa_srec, recs.data(), recs.size(), c->stream));
+    TRY(launch_msa_sites(c, recs.size(), (const MsaSitePair *)c->msa_srec.p, (const uint8_t *)c->rc_seq.p, (const uint32_t *)c->msa_words.p,
+                         (const uint32_t *)c->msa_width.p, (const uint32_t *)c->msa_col.p, (const uint32_t *)c->msa_scol.p,
+                         (const uint2 *)c->msa_sres.p, (uint8_t *)c->msa_sout.p, quals ? (uint8_t *)c->msa_sq.p : nullptr));
+    TRY(fetch(alleles + off[pb.i0], c->msa_sout.p, bytes));  // (synchronizes: the records and the strings are the next batch's)
+    if (quals) TRY(fetch(quals + off[pb.i0], c->msa_sq.p, bytes));
+  }
+  MCG_CHECK(hipStreamSynchronize(c->stream));
+  flush_timers(c);
+  return MC_OK;
+}
+
+int mc_nw_msa_sites_profile(mc_ctx *c, double *out, int reset) {
+  if (!c || !out) return MC_ERR_ARG;
+  (void)hipStreamSynchronize(c->stream);
+  flush_timers(c);
+  out[0] = c->fam_ms[F_NW_MSAS];
+  if (reset) c->fam_ms[F_NW_MSAS] = c->fam_n[F_NW_MSAS] = 0;
+  return MC_OK;
+}
+
 int mc_nw_msa_end(mc_ctx *c) {
   if (!c) return MC_ERR_ARG;
   msa_drop(c);
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   for (Buf *b : {&c->msa_width, &c->msa_col, &c->msa_words, &c->msa_bw, &c->msa_rec, &c->msa_out, &c->msa_cnt, &c->msa_wcnt,
-                 &c->msa_cdiff, &c->msa_crec, &c->msa_ctgt}) {
+                 &c->msa_cdiff, &c->msa_crec, &c->msa_ctgt, &c->msa_scol, &c->msa_sres, &c->msa_stgt, &c->msa_srec, &c->msa_sout,
+                 &c->msa_sq}) {
     if (b->p) (void)hipFree(b->p);
     *b = Buf{};
   }

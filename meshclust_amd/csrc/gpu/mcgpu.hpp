@@ -33,8 +33,9 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // pileup.hip, likewise part of F_NW and kept apart for mc_nw_pileup_profile; F_NW_MSAW / F_NW_MSAR:
 // the width + column kernels and the render kernel of msa.hip, part of F_NW, for mc_nw_msa_profile;
 // F_NW_MSAC: the counts kernels of msa.hip (mc_nw_msa_counts), part of F_NW, for mc_nw_msa_counts_profile;
-// F_NW_BAND: the score-only launches of the width search (nwband.hip), part of F_NW, for mc_nw_band_profile
-enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NW_MSAC, F_NW_BAND, F_NALL };
+// F_NW_BAND: the score-only launches of the width search (nwband.hip), part of F_NW, for mc_nw_band_profile;
+// F_NW_MSAS: the resolve and gather kernels of msa.hip (mc_nw_msa_sites), part of F_NW, for mc_nw_msa_sites_profile
+enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NW_MSAC, F_NW_BAND, F_NW_MSAS, F_NALL };
 
 // Classifier in the form the kernels consume (mc_classifier + the exact decision threshold).
 struct DevClassifier {
@@ -140,6 +141,21 @@ struct MsaCountPair {
 struct MsaCountTarget {
   uint64_t c_off, row0, col0, drow0;
   uint32_t L, W, depth, pad;
+};
+
+// One target of mc_nw_msa_sites (msa.hip): its S chosen columns at s_off of the call's site
+// buffers, row0 the first of its L + 1 widths and columns in the plan.
+struct MsaSiteTarget {
+  uint64_t row0, s_off;
+  uint32_t L, S;
+};
+
+// One pair of a gather batch of mc_nw_msa_sites: seq1 and its words as in MsaRow, row0 / s_off / S its
+// target's (MsaSiteTarget), lb the centre's length; its S bytes at out_off of the batch's outputs;
+// q_off: the read's offset in the loaded qualities (as loaded, whatever the strand).
+struct MsaSitePair {
+  uint64_t a_off, w_off, row0, s_off, out_off, q_off;
+  uint32_t la, lb, nw, S, a_rc, pad;
 };
 
 // A range of one array of the device lazy introsort (split.hip): partitioned (left >= 0:
@@ -250,8 +266,12 @@ struct mc_ctx {
   // msa_tp_off / msa_tp: every target's pairs in list order (nt + 1 offsets into m pair indices).
   // msa_cnt / msa_wcnt / msa_cdiff / msa_crec / msa_ctgt: a counts batch's column tables, its two
   // difference arrays, pair records and target records (mc_nw_msa_counts only).
+  // msa_scol / msa_sres / msa_stgt / msa_srec / msa_sout / msa_sq: a call's site columns, their
+  // resolved (row, slot + 1 or 0) and target records, a gather batch's pair records, alleles and
+  // weights (mc_nw_msa_sites only).
   bool msa_on = false;
   mcg::Buf msa_width, msa_col, msa_words, msa_bw, msa_rec, msa_out, msa_cnt, msa_wcnt, msa_cdiff, msa_crec, msa_ctgt;
+  mcg::Buf msa_scol, msa_sres, msa_stgt, msa_srec, msa_sout, msa_sq;
   std::vector<uint32_t> msa_a, msa_b, msa_targets, msa_tof, msa_nops, msa_tp;
   std::vector<uint64_t> msa_tp_off;
   std::vector<uint8_t> msa_minus;
@@ -401,6 +421,15 @@ int launch_msa_counts(mc_ctx *c, uint64_t npairs, const MsaCountPair *d_pairs, c
                       int32_t *d_ddel);
 int launch_msa_counts_finish(mc_ctx *c, uint32_t nt, const MsaCountTarget *d_tgts, const uint32_t *d_width, const uint32_t *d_col,
                              uint32_t *d_counts, const int32_t *d_deq, const int32_t *d_ddel);
+// msa.hip (mc_nw_msa_sites): per target the chosen columns d_sites resolved against the plan's
+// columns into d_res (row, slot + 1 or 0: what the counts write to channels 6 and 7); per pair of a
+// gather batch the non-gap bytes at its target's sites into d_out (pre-filled with the gap) and,
+// d_qout given, the loaded qualities beside them (pre-filled with 0).
+int launch_msa_sites_resolve(mc_ctx *c, uint32_t nt, const MsaSiteTarget *d_tgts, const uint32_t *d_width, const uint32_t *d_col,
+                             const uint32_t *d_sites, uint2 *d_res);
+int launch_msa_sites(mc_ctx *c, uint64_t npairs, const MsaSitePair *d_pairs, const uint8_t *d_rc, const uint32_t *d_words,
+                     const uint32_t *d_width, const uint32_t *d_col, const uint32_t *d_sites, const uint2 *d_res, uint8_t *d_out,
+                     uint8_t *d_qout);
 // abi_align.hip: forget mc_nw_msa_begin's plan (its device buffers stay for the next one)
 void msa_drop(mc_ctx *c);
 

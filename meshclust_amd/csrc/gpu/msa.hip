@@ -42,6 +42,20 @@
 // col[r] (the centre byte's class, channel 5), channels 6 and 7 are written, and every slot's
 // channel 5 becomes depth less its channels 0..4.  A run that would leave the pair's strings is
 // skipped and no column at or past W is touched: msa_render_kernel's rule.
+//
+// msa_sites_resolve_kernel / msa_sites_kernel (mc_nw_msa_sites): the block gathered at
+// a caller-chosen set of columns per target instead of rendered.  The resolve kernel, a wavefront per
+// target and a lane per site: the first row r with col[r] >= the column, by bisection; the site is
+// centre base r (slot 0) or slot column - (col[r] - w[r]) + 1 of site r -- what the finish kernel
+// writes to channels 6 and 7.  The gather kernel, a wavefront per pair over an output the host filled
+// with the gap (the weights with 0), the same walk; the lane that owns a run lower-bounds its
+// target's ascending site list at the run's first column and stores the bytes of the sites inside it:
+//   '=' / 'X' run of n at row j   the sites with slot 0 and r in [j, j + n): the base, its quality
+//   'D' run of n at row j         the same sites: the run's weight only, the byte stays a gap
+//   'I' run of n at row j         the sites at columns col[j] - w[j] + t, t < min(n, w[j]): the base
+//                                 seq1[i + t], its quality
+// Every non-gap byte is stored exactly once, by one lane, so the result depends on no order.  A run
+// that would leave the pair's strings is skipped and no offset at or past S is formed.
 #include "mcgpu.hpp"
 
 namespace mcg {
@@ -364,7 +378,129 @@ __global__ __launch_bounds__(64) void msa_counts_finish_kernel(const MsaCountTar
   }
 }
 
+__global__ __launch_bounds__(64) void msa_sites_resolve_kernel(const MsaSiteTarget *__restrict__ tgts, uint32_t nt,
+                                                               const uint32_t *__restrict__ width, const uint32_t *__restrict__ colarr,
+                                                               const uint32_t *__restrict__ sites, uint2 *__restrict__ res) {
+  const uint32_t k = blockIdx.x;
+  if (k >= nt) return;
+  const MsaSiteTarget tg = tgts[k];
+  const uint32_t *w = width + tg.row0, *col = colarr + tg.row0;
+  for (uint32_t s = threadIdx.x; s < tg.S; s += 64) {
+    const uint32_t pc = sites[tg.s_off + s];
+    uint32_t lo = 0, hi = tg.L;  // the first row whose column is not before pc (col[L] = W > pc)
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) / 2;
+      if (col[mid] < pc) lo = mid + 1;
+      else hi = mid;
+    }
+    const uint32_t c = col[lo];
+    res[tg.s_off + s] = make_uint2(lo, c == pc && lo < tg.L ? 0u : pc - (c - w[lo]) + 1);
+  }
+}
+
+struct SiteArgs {
+  const MsaSitePair *pairs;
+  uint32_t npairs;
+  const uint8_t *codes, *rc, *qual;
+  const uint32_t *words, *width, *col, *sites;
+  const uint2 *res;
+  uint8_t *out, *qout;
+};
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(64) void msa_sites_kernel(SiteArgs q) {
+  const uint32_t p = blockIdx.x;
+  if (p >= q.npairs) return;
+  const MsaSitePair pr = q.pairs[p];
+  const uint32_t S = pr.S;
+  if (S == 0) return;
+  const uint8_t *a = (pr.a_rc ? q.rc : q.codes) + pr.a_off;
+  const uint8_t *ql = WEIGHTED ? q.qual + pr.q_off : nullptr;
+  const uint32_t *w = q.width + pr.row0, *col = q.col + pr.row0;
+  const uint32_t *src = q.words + pr.w_off;
+  const uint32_t *st = q.sites + pr.s_off;
+  const uint2 *rs = q.res + pr.s_off;
+  uint8_t *o = q.out + pr.out_off, *oq = WEIGHTED ? q.qout + pr.out_off : nullptr;
+  const uint32_t la = pr.la, L = pr.lb, nw = pr.nw;
+  const bool rc = pr.a_rc != 0;
+  const int lane = (int)threadIdx.x;
+  auto Qs = [&](uint32_t i) -> uint32_t { return ql[rc ? la - 1 - i : i]; };  // i < la
+  auto lower = [&](uint32_t pc) {  // the first site at or after column pc (S: none)
+    uint32_t lo = 0, hi = S;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) / 2;
+      if (st[mid] < pc) lo = mid + 1;
+      else hi = mid;
+    }
+    return lo;
+  };
+  uint32_t ci = 0, cj = 0;  // bases consumed before this chunk
+  const uint32_t nchunk = (nw + 63) / 64;
+  for (uint32_t c = 0; c < nchunk; c++) {
+    const uint32_t kk = c * 64 + (uint32_t)lane;
+    const uint32_t wd = kk < nw ? src[kk] : 0u;
+    const uint32_t n = wd >> 4, op = wd & 15u;
+    const bool both = op == MC_CIGAR_EQ || op == MC_CIGAR_X, del = op == MC_CIGAR_D, ins = op == MC_CIGAR_I;
+    const uint32_t di = both || ins ? n : 0u, dj = both || del ? n : 0u;
+    const uint32_t si = wave_scan(di, lane), sj = wave_scan(dj, lane);
+    const uint32_t i0 = ci + si - di, j0 = cj + sj - dj;
+    ci += (uint32_t)__shfl((int)si, 63, 64);
+    cj += (uint32_t)__shfl((int)sj, 63, 64);
+    const bool ok = n > 0 && i0 + di <= la && j0 + dj <= L;
+    if (ok && ins) {
+      const uint32_t wj = w[j0], s0 = col[j0] - wj, cnt = min(n, wj);
+      for (uint32_t s = lower(s0); s < S; s++) {
+        const uint32_t t = st[s] - s0;
+        if (t >= cnt) break;
+        o[s] = base_char(a[i0 + t]);
+        if (WEIGHTED) oq[s] = (uint8_t)Qs(i0 + t);
+      }
+    } else if (ok && (both || (WEIGHTED && del))) {
+      uint32_t gq = 0;
+      if (WEIGHTED && del) {  // nwt_pileup_kernel's weight of a 'D' run with i0 read bases before it
+        uint32_t v = 0xffffffffu;
+        if (i0 > 0) v = Qs(i0 - 1);
+        if (i0 < la) v = min(v, Qs(i0));
+        gq = v == 0xffffffffu ? 0u : v;
+      }
+      if (both || gq)
+        for (uint32_t s = lower(col[j0]); s < S; s++) {
+          const uint2 x = rs[s];
+          if (x.x >= j0 + n) break;
+          if (x.y) continue;  // a slot between two columns of the run: the pair has no 'I' run there
+          const uint32_t i = i0 + (x.x - j0);
+          if (both) o[s] = base_char(a[i]);
+          if (WEIGHTED) oq[s] = (uint8_t)(both ? Qs(i) : gq);
+        }
+    }
+  }
+}
+
 }  // namespace
+
+int launch_msa_sites_resolve(mc_ctx *c, uint32_t nt, const MsaSiteTarget *d_tgts, const uint32_t *d_width, const uint32_t *d_col,
+                             const uint32_t *d_sites, uint2 *d_res) {
+  if (nt == 0) return MC_OK;
+  timed_begin(c);
+  msa_sites_resolve_kernel<<<nt, 64, 0, c->stream>>>(d_tgts, nt, d_width, d_col, d_sites, d_res);
+  MCG_CHECK(hipGetLastError());
+  timed_end(c, F_NW_MSAS);
+  return MC_OK;
+}
+
+int launch_msa_sites(mc_ctx *c, uint64_t npairs, const MsaSitePair *d_pairs, const uint8_t *d_rc, const uint32_t *d_words,
+                     const uint32_t *d_width, const uint32_t *d_col, const uint32_t *d_sites, const uint2 *d_res, uint8_t *d_out,
+                     uint8_t *d_qout) {
+  if (npairs == 0) return MC_OK;
+  SiteArgs q{d_pairs, (uint32_t)npairs, (const uint8_t *)c->codes.p, d_rc, (const uint8_t *)c->qual.p, d_words, d_width, d_col,
+             d_sites, d_res, d_out, d_qout};
+  timed_begin(c);
+  if (d_qout) msa_sites_kernel<true><<<(unsigned)npairs, 64, 0, c->stream>>>(q);
+  else msa_sites_kernel<false><<<(unsigned)npairs, 64, 0, c->stream>>>(q);
+  MCG_CHECK(hipGetLastError());
+  timed_end(c, F_NW_MSAS);
+  return MC_OK;
+}
 
 int launch_msa_width(mc_ctx *c, uint32_t m, const TracePair *d_pairs, const uint32_t *d_ops, const int32_t *d_res,
                      const uint64_t *d_rowbase, uint32_t *d_width) {

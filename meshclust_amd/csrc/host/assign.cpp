@@ -20,6 +20,7 @@
 #include "model.hpp"
 #include "revseq.hpp"
 #include "topk.hpp"
+#include "variants.hpp"
 #include "verify.hpp"
 
 namespace mc {
@@ -27,7 +28,8 @@ namespace mc {
 static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
     "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--consensus FILE] "
-    "[--pileup FILE] [--quality] [--msa FILE] [--profile FILE] [--band] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
+    "[--pileup FILE] [--quality] [--msa FILE] [--profile FILE] [--band] [--variants FILE] [--alleles FILE] [--haplotypes FILE] [--min-allele-frac X] "
+    "[--min-allele-count N] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
     "                  (implied by a version-2 model, saved by meshclust --both-strands: reads and centres are then\n"
     "                  scored once on their canonical rows and every hit's strand comes from mc_orient_pairs; with\n"
@@ -56,8 +58,17 @@ static const char *kUsage =
     "  --profile FILE  (implies --identity) that alignment counted per column, for centres with reads: centre, column,\n"
     "                  centre_pos, slot (0: a centre base; from 1: an inserted column before it), base (- inserted),\n"
     "                  depth, A, C, G, T, N, gap; with --quality (FASTQ reads) also wA wC wG wT wN wgap\n"
-    "  --band          (with --paf, --consensus, --pileup, --msa or --profile) record only a certified band of every\n"
-    "                  alignment's choices (mc_set_align_band): less scratch, more pairs per batch, no output file changes\n"
+    "  --band          (with --paf, --consensus, --pileup, --msa, --profile, --variants, --alleles or --haplotypes) record\n"
+    "                  only a certified band of every alignment's choices (mc_set_align_band): less scratch, more pairs per\n"
+    "                  batch, no output file changes\n"
+    "  --variants FILE  (implies --identity) the --profile lines of the variant sites of every centre with reads: the\n"
+    "                  columns whose second most frequent allele (A, C, G, T or gap) is seen --min-allele-count times or\n"
+    "                  more and in --min-allele-frac of the rows or more\n"
+    "  --alleles FILE  (implies --identity) one line per assigned read: read, centre, strand, its characters at its\n"
+    "                  centre's variant sites (. if it has none); with --quality a fifth column, their weights as Phred+33\n"
+    "  --haplotypes FILE  (implies --identity) per centre with a site, one line per distinct allele string seen\n"
+    "                  --min-allele-count times or more: centre, rank, count, depth, alleles\n"
+    "  --min-allele-frac X  (0 < X <= 1, default 0.2)   --min-allele-count N  (N >= 1, default 2)\n"
     "  reads and centres may be FASTA or FASTQ files (decided per file); without --quality the qualities are skipped\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
@@ -108,6 +119,27 @@ AssignOptions parse_assign_options(int argc, char **argv) {
     } else if (arg == "--profile" && has) {
       o.profile = argv[++i];
       o.identity = true;
+    } else if (arg == "--variants" && has) {
+      o.variants = argv[++i];
+      o.identity = true;
+    } else if (arg == "--alleles" && has) {
+      o.alleles = argv[++i];
+      o.identity = true;
+    } else if (arg == "--haplotypes" && has) {
+      o.haplotypes = argv[++i];
+      o.identity = true;
+    } else if (arg == "--min-allele-frac" && has) {
+      char *end = nullptr;
+      const char *txt = argv[++i];
+      o.min_allele_frac = strtod(txt, &end);
+      if (end == txt || *end || !(o.min_allele_frac > 0 && o.min_allele_frac <= 1))
+        throw Error(std::string("--min-allele-frac must be above 0 and at most 1\n") + kUsage, 1);
+    } else if (arg == "--min-allele-count" && has) {
+      char *end = nullptr;
+      const char *txt = argv[++i];
+      const long long v = strtoll(txt, &end, 10);
+      if (end == txt || *end || v < 1) throw Error(std::string("--min-allele-count must be 1 or more\n") + kUsage, 1);
+      o.min_allele_count = (uint64_t)v;
     } else {
       struct stat st;
       if (stat(argv[i], &st) == 0 && S_ISREG(st.st_mode)) o.reads.push_back(argv[i]);
@@ -117,9 +149,9 @@ AssignOptions parse_assign_options(int argc, char **argv) {
   if (o.model.empty() || o.centres.empty() || o.reads.empty())
     throw Error(std::string("--model, --centres and at least one reads file are required\n") + kUsage, 1);
   if ((o.top > 0) != !o.hits.empty()) throw Error(std::string("--top K and --hits FILE are given together\n") + kUsage, 1);
-  if (o.quality && o.consensus.empty() && o.pileup.empty() && o.profile.empty())
+  if (o.quality && o.consensus.empty() && o.pileup.empty() && o.profile.empty() && !o.any_variants())
     throw Error(std::string("--quality needs --consensus FILE and/or --pileup FILE (or --profile FILE)\n") + kUsage, 1);
-  if (o.band && o.paf.empty() && o.consensus.empty() && o.pileup.empty() && o.msa.empty() && o.profile.empty())
+  if (o.band && o.paf.empty() && o.consensus.empty() && o.pileup.empty() && o.msa.empty() && o.profile.empty() && !o.any_variants())
     throw Error(std::string("--band needs --paf, --consensus, --pileup, --msa or --profile\n") + kUsage, 1);
   return o;
 }
@@ -333,73 +365,188 @@ static void pileup_outputs(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std
   if (!opt.pileup.empty()) write_text(opt.pileup, tsv);
 }
 
-// --profile: the plan of msa_output counted per column (mc_nw_msa_counts), read in ranges of targets
-// whose tables stay within 64 MiB on the host (a wider target alone), one line per column.
-static void profile_output(mc_ctx *ctx, const Dataset &ds, const std::vector<uint32_t> &targets, const std::vector<uint64_t> &W,
-                           const std::vector<uint64_t> &depth, const AssignOptions &opt, AssignResult &r) {
-  const uint32_t nt = (uint32_t)targets.size();
-  const uint64_t col_bytes = (uint64_t)MC_MSA_CH * 4 * (opt.quality ? 2 : 1), kWindow = 64ull << 20;
-  r.profile = true;
-  r.profile_centres = nt;
-  FILE *f = fopen(opt.profile.c_str(), "w");
-  if (!f) throw Error("cannot write " + opt.profile + ": " + strerror(errno), 1);
-  struct Close {
-    FILE *&f;
-    ~Close() {
-      if (f) fclose(f);
-    }
-  } closer{f};
-  std::string text;
+// one line of --profile (and of --variants): column c (0-based) of the centre `name` with bytes cen, x its
+// MC_MSA_CH counters, y its weights or NULL
+static void profile_line(std::string &text, const std::string &name, const std::vector<uint8_t> &cen, uint64_t c, uint64_t depth,
+                         const uint32_t *x, const uint32_t *y) {
   char num[256];
-  auto flush = [&](bool all) {
+  text.append(name);
+  snprintf(num, sizeof num, "\t%llu\t%u\t%u\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u", (unsigned long long)(c + 1), x[6] + 1, x[7],
+           x[7] == 0 && x[6] < cen.size() ? pileup_base_char(cen[x[6]]) : '-', (unsigned long long)depth, x[0], x[1], x[2], x[3], x[4],
+           x[5]);
+  text += num;
+  if (y) {
+    snprintf(num, sizeof num, "\t%u\t%u\t%u\t%u\t%u\t%u", y[0], y[1], y[2], y[3], y[4], y[5]);
+    text += num;
+  }
+  text += '\n';
+}
+
+// a text file written through a buffer of about 1 MiB; an empty path opens nothing and drops what is written
+struct TextFile {
+  std::string path, text;
+  FILE *f = nullptr;
+  explicit TextFile(const std::string &p) : path(p) {
+    if (path.empty()) return;
+    f = fopen(path.c_str(), "w");
+    if (!f) throw Error("cannot write " + path + ": " + strerror(errno), 1);
+  }
+  ~TextFile() {
+    if (f) fclose(f);
+  }
+  bool on() const { return f != nullptr; }
+  void flush(bool all) {
+    if (!f) text.clear();
     if (text.size() < (all ? 1u : 1u << 20)) return;
-    if (fwrite(text.data(), 1, text.size(), f) != text.size()) throw Error("cannot write " + opt.profile, 1);
+    if (fwrite(text.data(), 1, text.size(), f) != text.size()) throw Error("cannot write " + path, 1);
     text.clear();
-  };
-  std::vector<uint32_t> counts, wcounts;
+  }
+  void close() {
+    flush(true);
+    FILE *done = f;
+    f = nullptr;
+    if (done && fclose(done) != 0) throw Error("cannot write " + path, 1);
+  }
+};
+
+// every target's variant sites (variants.hpp), mc_nw_msa_sites' two arguments
+struct SiteLists {
+  std::vector<uint64_t> site_off;
+  std::vector<uint32_t> sites;
+};
+
+// One pass over the plan of msa_output counted per column (mc_nw_msa_counts), read in ranges of targets
+// whose tables stay within 64 MiB on the host (a wider target alone).  write_profile: --profile, one line per
+// column.  sl given (--variants / --alleles / --haplotypes): every target's sites by variant_sites into *sl,
+// and their lines, the profile's own, to --variants.  Both in one run share the pass: the tables come back once.
+static void profile_output(mc_ctx *ctx, const Dataset &ds, const std::vector<uint32_t> &targets, const std::vector<uint64_t> &W,
+                           const std::vector<uint64_t> &depth, const AssignOptions &opt, AssignResult &r, bool write_profile,
+                           SiteLists *sl) {
+  const uint32_t nt = (uint32_t)targets.size();
+  TextFile pf(write_profile ? opt.profile : std::string()), vf(sl ? opt.variants : std::string());
+  const bool weights = opt.quality && (pf.on() || vf.on());
+  const uint64_t col_bytes = (uint64_t)MC_MSA_CH * 4 * (opt.quality ? 2 : 1), kWindow = 64ull << 20;
+  if (write_profile) {
+    r.profile = true;
+    r.profile_centres = nt;
+  }
+  if (sl) sl->site_off.assign((size_t)nt + 1, 0);
+  std::vector<uint32_t> counts, wcounts, st;
   std::vector<uint64_t> off;
   for (uint32_t t0 = 0, t1; t0 < nt; t0 = t1) {
     uint64_t cols = 0;
     for (t1 = t0; t1 < nt && (t1 == t0 || (cols + W[t1]) * col_bytes <= kWindow); t1++) cols += W[t1];
     counts.resize(cols * MC_MSA_CH);
-    if (opt.quality) wcounts.resize(cols * MC_MSA_CH);
+    if (weights) wcounts.resize(cols * MC_MSA_CH);
     off.resize((size_t)(t1 - t0) + 1);
-    check(mc_nw_msa_counts(ctx, t0, t1 - t0, off.data(), counts.data(), opt.quality ? wcounts.data() : nullptr, cols), "mc_nw_msa_counts");
+    check(mc_nw_msa_counts(ctx, t0, t1 - t0, off.data(), counts.data(), weights ? wcounts.data() : nullptr, cols), "mc_nw_msa_counts");
     for (uint32_t t = t0; t < t1; t++) {
-      const uint32_t j = targets[t];
-      const std::vector<uint8_t> cen = expanded_bytes(ds, j);
-      const std::string name(ds.headers[j].substr(1));
-      for (uint64_t c = 0; c < W[t]; c++) {
-        const uint32_t *x = counts.data() + (off[t - t0] + c) * MC_MSA_CH;
-        text.append(name);
-        snprintf(num, sizeof num, "\t%llu\t%u\t%u\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u", (unsigned long long)(c + 1), x[6] + 1, x[7],
-                 x[7] == 0 && x[6] < cen.size() ? pileup_base_char(cen[x[6]]) : '-', (unsigned long long)depth[t], x[0], x[1], x[2], x[3],
-                 x[4], x[5]);
-        text += num;
-        if (opt.quality) {
-          const uint32_t *y = wcounts.data() + (off[t - t0] + c) * MC_MSA_CH;
-          snprintf(num, sizeof num, "\t%u\t%u\t%u\t%u\t%u\t%u", y[0], y[1], y[2], y[3], y[4], y[5]);
-          text += num;
-        }
-        text += '\n';
+      const uint32_t *tab = counts.data() + off[t - t0] * MC_MSA_CH;
+      const uint32_t *wtab = weights ? wcounts.data() + off[t - t0] * MC_MSA_CH : nullptr;
+      st.clear();
+      if (sl) {
+        st = variant_sites(tab, W[t], opt.min_allele_frac, opt.min_allele_count);
+        sl->sites.insert(sl->sites.end(), st.begin(), st.end());
+        sl->site_off[t + 1] = sl->sites.size();
+        r.variant_centres += !st.empty();
+        r.variant_sites += st.size();
       }
-      r.profile_columns += W[t];
-      flush(false);
+      if (write_profile) r.profile_columns += W[t];
+      if (!pf.on() && (!vf.on() || st.empty())) continue;
+      const std::vector<uint8_t> cen = expanded_bytes(ds, targets[t]);
+      const std::string name(ds.headers[targets[t]].substr(1));
+      if (pf.on())
+        for (uint64_t c = 0; c < W[t]; c++)
+          profile_line(pf.text, name, cen, c, depth[t], tab + c * MC_MSA_CH, wtab ? wtab + c * MC_MSA_CH : nullptr);
+      if (vf.on())
+        for (uint32_t c : st)
+          profile_line(vf.text, name, cen, c, depth[t], tab + (uint64_t)c * MC_MSA_CH, wtab ? wtab + (uint64_t)c * MC_MSA_CH : nullptr);
+      pf.flush(false);
+      vf.flush(false);
     }
   }
-  flush(true);
-  FILE *done = f;
-  f = nullptr;
-  if (fclose(done) != 0) throw Error("cannot write " + opt.profile, 1);
+  pf.close();
+  vf.close();
+}
+
+// --alleles / --haplotypes on the plan of msa_output, at the sites profile_output left in sl: mc_nw_msa_sites
+// over ranges of pairs whose bytes stay within 32 MiB (a pair of more alone): a line per pair to --alleles, and
+// a target's strings, complete once its last pair is read (the pairs are sorted by target), through haplotypes
+// to --haplotypes.
+static void variants_output(mc_ctx *ctx, const Dataset &ds, const std::vector<uint32_t> &targets, const std::vector<uint64_t> &depth,
+                            const std::vector<uint32_t> &qa, const std::vector<uint8_t> &qm, const std::vector<uint32_t> &tof,
+                            const SiteLists &sl, const AssignOptions &opt, AssignResult &r) {
+  const uint64_t m = qa.size(), kWindow = 32ull << 20;
+  const std::vector<uint64_t> &site_off = sl.site_off;
+  const std::vector<uint32_t> &sites = sl.sites;
+  r.variants = true;
+  TextFile af(opt.alleles), hf(opt.haplotypes);
+  std::vector<uint64_t> off;
+  if (!af.on() && !hf.on()) return;
+  auto nsite = [&](uint64_t k) { return site_off[tof[k] + 1] - site_off[tof[k]]; };
+  const uint64_t per = opt.quality && af.on() ? 2 : 1;
+  std::vector<uint8_t> al, ql, strings;  // strings: the allele strings of the target being read, one after the other
+  char num[96];
+  for (uint64_t k0 = 0, k1; k0 < m; k0 = k1) {
+    uint64_t bytes = 0;
+    for (k1 = k0; k1 < m && (k1 == k0 || (bytes + nsite(k1)) * per <= kWindow); k1++) bytes += nsite(k1);
+    al.resize(bytes);
+    if (per == 2) ql.resize(bytes);
+    off.resize((size_t)(k1 - k0) + 1);
+    check(mc_nw_msa_sites(ctx, site_off.data(), sites.data(), k0, k1 - k0, al.data(), per == 2 ? ql.data() : nullptr, bytes, off.data()),
+          "mc_nw_msa_sites");
+    r.allele_bytes += bytes * per;
+    for (uint64_t k = k0; k < k1; k++) {
+      const uint32_t t = tof[k];
+      const uint64_t S = nsite(k);
+      const uint8_t *x = al.data() + off[k - k0];
+      if (af.on()) {
+        af.text.append(ds.headers[qa[k]].substr(1));
+        af.text += '\t';
+        af.text.append(ds.headers[targets[t]].substr(1));
+        af.text += qm[k] ? "\t-\t" : "\t+\t";
+        if (S) af.text.append((const char *)x, S);
+        else af.text += '.';
+        if (per == 2) {
+          af.text += '\t';
+          for (uint64_t s = 0; s < S; s++) af.text += (char)(ql[off[k - k0] + s] + 33);
+          if (!S) af.text += '.';
+        }
+        af.text += '\n';
+        af.flush(false);
+      }
+      if (hf.on() && S) {
+        strings.insert(strings.end(), x, x + S);
+        if (k + 1 == m || tof[k + 1] != t) {  // the target's last pair
+          const std::string name(ds.headers[targets[t]].substr(1));
+          uint32_t rank = 0;
+          for (const auto &h : haplotypes(strings.data(), depth[t], S, opt.min_allele_count)) {
+            hf.text.append(name);
+            snprintf(num, sizeof num, "\t%u\t%llu\t%llu\t", ++rank, (unsigned long long)h.second, (unsigned long long)depth[t]);
+            hf.text += num;
+            hf.text += h.first;
+            hf.text += '\n';
+          }
+          strings.clear();
+          hf.flush(false);
+        }
+      }
+    }
+  }
+  af.close();
+  hf.close();
 }
 
 // --msa / --profile: the pairs (read pa, centre pb < C, strand pm) of the assigned reads, sorted by
 // centre (input order kept), through one mc_nw_msa_begin with the centres that have a read as
 // targets.  --msa: the rows come back through two windows of at most 32 MiB, one over the centre rows
 // and one over the pair rows, and are written block by block.  --profile: profile_output on the same
-// plan; beside --msa its time goes to r.profile_ms.
+// plan; --variants / --alleles / --haplotypes: variants_output on it.  t0: when the caller began to list the
+// pairs; that, the sort and the begin are timed with the first output that is asked for, the others on their
+// own (r.msa_ms, r.profile_ms, r.variants_ms; the caller adds what follows the last of them).
 static void msa_output(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::vector<uint32_t> &pa, const std::vector<uint32_t> &pb,
-                       const std::vector<uint8_t> &pm, const AssignOptions &opt, AssignResult &r) {
+                       const std::vector<uint8_t> &pm, const AssignOptions &opt, AssignResult &r,
+                       std::chrono::steady_clock::time_point t0) {
   const size_t m = pa.size();
   std::vector<uint64_t> from((size_t)C + 1, 0);  // a centre's pairs after the sort: from[c] .. from[c + 1]
   for (size_t p = 0; p < m; p++) from[pb[p] + 1]++;
@@ -430,8 +577,27 @@ static void msa_output(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::ve
   } ender{ctx};
   std::vector<uint64_t> depths(nt);
   for (uint32_t t = 0; t < nt; t++) depths[t] = from[targets[t] + 1] - from[targets[t]];
-  if (opt.msa.empty()) {  // --profile alone (the caller times the whole pass)
-    profile_output(ctx, ds, targets, W, depths, opt, r);
+  // the sort and the begin count with the first output (mark starts at the caller's t0); every later one is timed on its own
+  auto mark = t0;
+  auto lap = [&](double &ms) {
+    ms = ms_since(mark);
+    mark = std::chrono::steady_clock::now();
+  };
+  auto rest = [&]() {  // --profile, then the three variant files, on the same plan and, given together, one pass over its tables
+    const bool var = opt.any_variants();
+    SiteLists sl;
+    if (!opt.profile.empty()) {
+      profile_output(ctx, ds, targets, W, depths, opt, r, true, var ? &sl : nullptr);
+      lap(r.profile_ms);
+    }
+    if (var) {
+      if (opt.profile.empty()) profile_output(ctx, ds, targets, W, depths, opt, r, false, &sl);
+      variants_output(ctx, ds, targets, depths, qa, qm, tof, sl, opt, r);
+      lap(r.variants_ms);
+    }
+  };
+  if (opt.msa.empty()) {
+    rest();
     return;
   }
   r.msa = true;
@@ -493,11 +659,8 @@ static void msa_output(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::ve
   FILE *done = f;
   f = nullptr;
   if (fclose(done) != 0) throw Error("cannot write " + opt.msa, 1);
-  if (!opt.profile.empty()) {
-    const auto t0 = std::chrono::steady_clock::now();
-    profile_output(ctx, ds, targets, W, depths, opt, r);
-    r.profile_ms = ms_since(t0);
-  }
+  lap(r.msa_ms);
+  rest();
 }
 
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
@@ -801,7 +964,7 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
     }
   }
   r.identity_ms = ms_since(t0);
-  if (!opt.msa.empty() || !opt.profile.empty()) {  // a pass of its own, over the pairs --consensus takes
+  if (!opt.msa.empty() || !opt.profile.empty() || opt.any_variants()) {  // a pass of its own, over the pairs --consensus takes
     t0 = std::chrono::steady_clock::now();
     std::vector<uint32_t> pa, pb;
     std::vector<uint8_t> pm;
@@ -811,9 +974,11 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
         pb.push_back(best[q]);
         pm.push_back(opt.both_strands ? strand[q] : 0);
       }
-    msa_output(ctx, ds, (uint32_t)C, pa, pb, pm, opt, r);
-    if (r.msa) r.msa_ms = ms_since(t0) - r.profile_ms;  // (the begin counts with the first output)
-    else r.profile_ms = ms_since(t0);
+    msa_output(ctx, ds, (uint32_t)C, pa, pb, pm, opt, r, t0);
+    // the whole pass is accounted for: what follows the last output (mc_nw_msa_end) goes where it went before
+    // the variant files, to msa beside --msa, else to profile
+    const double tail = ms_since(t0) - (r.msa_ms + r.profile_ms + r.variants_ms);
+    (r.msa ? r.msa_ms : r.profile ? r.profile_ms : r.variants_ms) += tail;
   }
   t0 = std::chrono::steady_clock::now();
   // one line per read, in input order: read header, centre header or *, cluster index or -1,
@@ -891,7 +1056,8 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
 
 std::string assign_stats_json(const AssignResult &r) {
   // (one strand, no --top, no --identity: exactly the keys there were before any of the options)
-  char b[2176], s[704] = "", idms[48] = "", msa[224] = "", msams[48] = "", prof[128] = "", profms[48] = "", band[224] = "";
+  char b[2560], s[704] = "", idms[48] = "", msa[224] = "", msams[48] = "", prof[128] = "", profms[48] = "", band[224] = "";
+  char var[192] = "", varms[48] = "";
   int n = 0;
   if (r.strands != MC_STRAND_PLUS)
     n = snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
@@ -925,14 +1091,19 @@ std::string assign_stats_json(const AssignResult &r) {
     snprintf(band, sizeof band, ", \"band_pairs\": %llu, \"band_full\": %llu, \"band_launches\": %llu, \"band_w_sum\": %llu",
              (unsigned long long)r.band_pairs, (unsigned long long)r.band_full, (unsigned long long)r.band_launches,
              (unsigned long long)r.band_w_sum);
+  if (r.variants) {  // after every key there was before --variants / --alleles / --haplotypes
+    snprintf(var, sizeof var, ", \"variant_centres\": %llu, \"variant_sites\": %llu, \"allele_bytes\": %llu",
+             (unsigned long long)r.variant_centres, (unsigned long long)r.variant_sites, (unsigned long long)r.allele_bytes);
+    snprintf(varms, sizeof varms, ", \"variants\": %.3f", r.variants_ms);
+  }
   snprintf(b, sizeof b,
            "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, %s\"k\": %d, \"width\": %d, "
            "\"path\": \"%s\", \"candidate_pairs\": %llu, \"fallback_pairs\": %llu, \"device_us\": %llu, "
-           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f%s%s}%s%s%s}",
+           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f%s%s%s}%s%s%s%s}",
            (unsigned long long)r.reads, (unsigned long long)r.centres, (unsigned long long)r.assigned,
            (unsigned long long)(r.reads - r.assigned), s, r.k, r.width, r.path.c_str(), (unsigned long long)r.candidates,
            (unsigned long long)r.fallbacks, (unsigned long long)r.device_us, r.parse_ms, r.upload_ms, r.kmer_ms,
-           r.assign_ms, idms, r.write_ms, msams, profms, msa, prof, band);
+           r.assign_ms, idms, r.write_ms, msams, profms, varms, msa, prof, band, var);
   return b;
 }
 

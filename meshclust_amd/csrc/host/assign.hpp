@@ -25,7 +25,13 @@ struct AssignOptions {
   bool quality = false;       // --quality (with consensus and/or pileup; FASTQ reads): the pile-up weighed by base quality
   std::string msa;            // --msa FILE (implies identity): every centre's reads laid out in common columns, aligned FASTA
   std::string profile;        // --profile FILE (implies identity): the column profile of every centre's alignment, TSV
-  bool band = false;          // --band (with paf, consensus, pileup, msa or profile): the certified band for the alignments
+  bool band = false;          // --band (with paf, consensus, pileup, msa, profile or one of the three below): the certified band
+  std::string variants;       // --variants FILE (implies identity): the profile's lines of every centre's variant sites, TSV
+  std::string alleles;        // --alleles FILE (implies identity): every assigned read's characters at its centre's sites, TSV
+  std::string haplotypes;     // --haplotypes FILE (implies identity): the distinct allele strings of every centre with sites, TSV
+  double min_allele_frac = 0.2;    // --min-allele-frac X (0 < X <= 1) and --min-allele-count N (N >= 1): variants.hpp's rule
+  uint64_t min_allele_count = 2;
+  bool any_variants() const { return !variants.empty() || !alleles.empty() || !haplotypes.empty(); }
 };
 
 struct AssignResult {
@@ -53,8 +59,10 @@ struct AssignResult {
   uint64_t profile_centres = 0, profile_columns = 0;
   bool band = false;             // --band: pairs planned banded and full, search launches, the sum of the planned widths
   uint64_t band_pairs = 0, band_full = 0, band_launches = 0, band_w_sum = 0;
+  bool variants = false;         // --variants / --alleles / --haplotypes: centres with a site, their sites, bytes of mc_nw_msa_sites
+  uint64_t variant_centres = 0, variant_sites = 0, allele_bytes = 0;
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
-  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0, msa_ms = 0, profile_ms = 0;
+  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0, msa_ms = 0, profile_ms = 0, variants_ms = 0;
 };
 
 // Throws mc::Error (bad options: code 1 with the usage text in what()).
@@ -117,7 +125,19 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // r + 1 (L + 1 after the last base), slot t + 1 and base '-'.  With quality (then also accepted
 // beside profile alone) every line gains wA wC wG wT wN wgap.  The stats gain, after every other
 // key, "profile_centres" and "profile_columns", and the phases "profile".
-// With band (it needs paf, consensus, pileup, msa or profile: parse_assign_options, usage error) the context is
+// With variants, alleles or haplotypes (each implies identity; they share msa's and profile's mc_nw_msa_begin and
+// change no other output) every centre's profile goes through variant_sites (variants.hpp) at min_allele_frac and
+// min_allele_count, whichever of the three files is asked for.  variants gets, for every centre with reads, the
+// lines profile would write for its site columns and no others, byte for byte (six weights more with quality,
+// which is then accepted beside any of the three).  alleles gets one line per assigned read, centres in
+// centres-file order and their reads in input order: read, centre, strand (+ or -), and the read's characters at
+// its centre's sites (mc_nw_msa_sites, read in ranges of pairs whose bytes stay within 32 MiB), "." for a centre
+// without sites; with quality a fifth column, the weights as Phred+33.  haplotypes gets, per centre with a site,
+// one line per distinct allele string seen min_allele_count times or more, by count descending and then by
+// bytes: centre, rank (from 1), count, depth, alleles.  The stats gain, after every other key, "variant_centres"
+// (centres with a site), "variant_sites" and "allele_bytes" (the bytes mc_nw_msa_sites returned), and the phases
+// "variants".
+// With band (it needs paf, consensus, pileup, msa, profile, variants, alleles or haplotypes: parse_assign_options, usage error) the context is
 // set to mc_set_align_band 1 for the run and back to 0 at its end: every alignment pass plans a width per pair
 // and records the certified band alone.  No output file changes.  The stats gain, after every other key,
 // "band_pairs", "band_full", "band_launches" and "band_w_sum" (mc_nw_band_profile over the run).

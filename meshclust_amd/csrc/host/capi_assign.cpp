@@ -14,12 +14,26 @@ extern "C" {
 // (assign.hpp run_assign): writes the TSV to `tsv` and, if `unassigned` is non-NULL, the
 // unassigned reads as FASTA.  The JSON summary goes to stats (cap bytes).  Returns 0 or an
 // error code with {"error": ...} in stats; an error never ends the calling process.
+struct VariantArgs {  // mcl_assign_variants' own arguments; the defaults are "none of them"
+  const char *variants = nullptr, *alleles = nullptr, *haplotypes = nullptr;
+  double min_allele_frac = 0.2;
+  long long min_allele_count = 2;
+};
+
 static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
                         int threads, const char *tsv, const char *unassigned, bool both_strands, int top, const char *hits,
                         int identity, double min_identity, const char *paf, const char *consensus, const char *pileup,
-                        bool quality, const char *msa, const char *profile, bool band, char *stats, int cap) {
+                        bool quality, const char *msa, const char *profile, bool band, char *stats, int cap,
+                        const VariantArgs &va = VariantArgs()) {
   try {
     mc::AssignOptions opt;
+    if (va.variants) opt.variants = va.variants;
+    if (va.alleles) opt.alleles = va.alleles;
+    if (va.haplotypes) opt.haplotypes = va.haplotypes;
+    if (!(va.min_allele_frac > 0 && va.min_allele_frac <= 1) || va.min_allele_count < 1)
+      throw mc::Error("mcl_assign_variants: min_allele_frac is above 0 and at most 1, min_allele_count 1 or more", 1);
+    opt.min_allele_frac = va.min_allele_frac;
+    opt.min_allele_count = (uint64_t)va.min_allele_count;
     opt.quality = quality;
     opt.band = band;
     if (msa) opt.msa = msa;
@@ -34,7 +48,7 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
       throw mc::Error("mcl_assign_top: top (1 .. MC_ASSIGN_MAX_TOP) and hits are given together", 1);
     if (!(min_identity <= 1)) throw mc::Error("mcl_assign_identity: min_identity is 0 .. 1 (negative: off)", 1);
     opt.min_identity = min_identity < 0 ? -1 : min_identity;
-    opt.identity = identity != 0 || min_identity >= 0 || !opt.paf.empty() || !opt.consensus.empty() || !opt.pileup.empty() || !opt.msa.empty() || !opt.profile.empty();
+    opt.identity = identity != 0 || min_identity >= 0 || !opt.paf.empty() || !opt.consensus.empty() || !opt.pileup.empty() || !opt.msa.empty() || !opt.profile.empty() || opt.any_variants();
     opt.model = model ? model : "";
     opt.centres = centres ? centres : "";
     for (int i = 0; i < nreads; i++) opt.reads.push_back(reads[i]);
@@ -43,9 +57,9 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
     if (unassigned) opt.unassigned = unassigned;
     opt.quiet = true;
     if (opt.model.empty() || opt.centres.empty() || opt.reads.empty()) throw mc::Error("mcl_assign: model, centres and reads are required", 1);
-    if (quality && opt.consensus.empty() && opt.pileup.empty() && opt.profile.empty())
+    if (quality && opt.consensus.empty() && opt.pileup.empty() && opt.profile.empty() && !opt.any_variants())
       throw mc::Error("mcl_assign_qconsensus: quality needs consensus and/or pileup (or profile)", 1);
-    if (band && opt.paf.empty() && opt.consensus.empty() && opt.pileup.empty() && opt.msa.empty() && opt.profile.empty())
+    if (band && opt.paf.empty() && opt.consensus.empty() && opt.pileup.empty() && opt.msa.empty() && opt.profile.empty() && !opt.any_variants())
       throw mc::Error("mcl_assign_band: band needs paf, consensus, pileup, msa or profile", 1);
     const mc::AssignResult r = mc::run_assign(ctx, opt);
     if (stats && cap > 0) snprintf(stats, cap, "%s", mc::assign_stats_json(r).c_str());
@@ -165,6 +179,28 @@ int mcl_assign_band(mc_ctx *ctx, const char *model, const char *centres, const c
                     const char *profile, int band, char *stats, int cap) {
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
                       min_identity, paf, consensus, pileup, quality != 0, msa, profile, band != 0, stats, cap);
+}
+
+// mcl_assign_band with meshclust-assign's --variants `variants`, --alleles `alleles` and --haplotypes `haplotypes`
+// (mc_nw_msa_counts, variants.hpp and mc_nw_msa_sites over the plan --msa and --profile use; each implies identity,
+// each may be NULL) at --min-allele-frac `min_allele_frac` (above 0, at most 1) and --min-allele-count
+// `min_allele_count` (1 or more): the profile lines of every centre's variant sites, every assigned read's
+// characters there, and the distinct allele strings per centre; quality and band are then accepted beside any
+// of the three.  The summary gains, after every other key, "variant_centres", "variant_sites", "allele_bytes"
+// and the "variants" phase.  All three NULL (at any valid thresholds; the defaults are 0.2 and 2) is mcl_assign_band.
+int mcl_assign_variants(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
+                        const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
+                        double min_identity, const char *paf, const char *consensus, const char *pileup, int quality, const char *msa,
+                        const char *profile, int band, const char *variants, const char *alleles, const char *haplotypes,
+                        double min_allele_frac, long long min_allele_count, char *stats, int cap) {
+  VariantArgs va;
+  va.variants = variants;
+  va.alleles = alleles;
+  va.haplotypes = haplotypes;
+  va.min_allele_frac = min_allele_frac;
+  va.min_allele_count = min_allele_count;
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
+                      min_identity, paf, consensus, pileup, quality != 0, msa, profile, band != 0, stats, cap, va);
 }
 
 // Records ids[0..n) of a parsed dataset (mcl_parse) as FASTA: header lines unchanged, each
