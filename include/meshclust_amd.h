@@ -366,6 +366,21 @@ int mc_nw_identity_strands(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, co
                            double *ident, int32_t *len, int32_t *ids);
 
 /*
+ * The multiset q-gram intersection of mc_nw_identity_strands' pairs: common[i] = the sum over the
+ * 4^q q-grams g of min(occurrences of g in seq1, occurrences of g in seq2), seq1 = point a[i] or
+ * its minus-strand string (a_minus[i] != 0; NULL: all plus), seq2 = point b[i].  q is 1 .. 7.
+ * common[i] is MC_QGRAM_NA where either string holds a byte outside 0..3 or is shorter than q.
+ * An alignment with L columns, I of them identities, has C_q >= q * I - (q - 1) * (L + 1), so a
+ * small count proves an identity below a cutoff without aligning (host/qscreen.hpp, DESIGN.md
+ * 3.15).  One workgroup per pair, a 4^q-entry table of counters in LDS.  Errors are
+ * mc_nw_identity's: no sequences MC_ERR_STATE, an id >= n or q out of range MC_ERR_ARG, m = 0
+ * MC_OK; a read of 2^31 bases or more MC_ERR_UNSUPPORTED.  Timed as "pairs" (mc_timers).
+ */
+#define MC_QGRAM_NA 0xffffffffu
+int mc_qgram_common(mc_ctx *ctx, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m, int q,
+                    uint32_t *common);
+
+/*
  * THE ALIGNMENT of a pair is the chain of predecessor choices along which GlobAlignE's (path
  * length, identities) payload reaches (la, lb): the reference keeps no path, but with its fixed
  * tie rules (M before X before Y into M, M before the gap into a gap, the first maximum of M, X, Y

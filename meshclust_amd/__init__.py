@@ -37,6 +37,7 @@ PILEUP_CH = 8  # MC_PILEUP_CH: counters per row of mc_nw_pileup_strands' table
 MSA_GAP = ord("-")  # MC_MSA_GAP: the gap byte of mc_nw_msa_rows
 MSA_CH = 8  # MC_MSA_CH: counters per column of mc_nw_msa_counts
 QUAL_MAX = 93  # MC_QUAL_MAX: the largest Phred value mc_load_qualities takes
+QGRAM_NA = 0xFFFFFFFF  # MC_QGRAM_NA: mc_qgram_common's "not available"
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
 
 
@@ -103,7 +104,7 @@ def gpu_lib():
                      "mc_comm_stats", "mc_comm_destroy", "mc_sync", "mc_assign", "mc_assign_strands",
                      "mc_revcomp_rows", "mc_assign_top", "mc_revcomp_sequences", "mc_nw_identity_strands",
                      "mc_nw_align_strands", "mc_nw_align_profile", "mc_nw_pileup_strands", "mc_nw_pileup_profile",
-                     "mc_kmer_max_strands", "mc_kmer_build_strands", "mc_orient_pairs"):
+                     "mc_kmer_max_strands", "mc_kmer_build_strands", "mc_orient_pairs", "mc_qgram_common"):
             getattr(lib, name).restype = C.c_int
         lib.mc_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
         lib.mc_comm_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -119,6 +120,7 @@ def gpu_lib():
         lib.mc_revcomp_sequences.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.mc_nw_identity_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
+        lib.mc_qgram_common.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
         lib.mc_nw_align_strands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                             C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mc_nw_align_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -620,6 +622,17 @@ class Engine:
                                                _p(ids)), "mc_nw_identity_strands")
         return ident, ln, ids
 
+    def qgram_common(self, a, b, q, a_minus=None):
+        """mc_qgram_common: the multiset q-gram intersection of nw_identity_strands' pairs (uint32;
+        QGRAM_NA where a string holds a byte outside 0..3 or is shorter than q)."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        am = None if a_minus is None else np.ascontiguousarray(a_minus, np.uint8)
+        assert len(a) == len(b) and (am is None or len(am) == len(a))
+        out = np.zeros(len(a), np.uint32)
+        self._ck(self.lib.mc_qgram_common(self.ctx, _p(a), _p(b), _p(am), C.c_uint64(len(a)), int(q), _p(out)), "mc_qgram_common")
+        return out
+
     def nw_align_strands(self, a, b, a_minus=None, cigar=True):
         """mc_nw_align_strands: the alignments behind nw_identity_strands -> (cigar, cig_off, score,
         len, ids).  ``cigar``: uint32 words run << 4 | op (CIGAR_I 1, CIGAR_D 2, CIGAR_EQ 7,
@@ -1047,6 +1060,20 @@ class Dataset:
                                            err, 1024)
         if rc != 0:
             raise MCError("mcl_label_identities failed (%d): %s" % (rc, err.value.decode()))
+        return out
+
+    def qscreen_common(self, a, b, q, a_minus=None):
+        """mcl_qscreen_common: host/qscreen.hpp's count of the pairs, the host twin of
+        Engine.qgram_common, from the parsed 2-bit words."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        am = None if a_minus is None else np.ascontiguousarray(a_minus, np.uint8)
+        assert len(a) == len(b) and (am is None or len(am) == len(a))
+        out = np.zeros(len(a), np.uint32)
+        self.lib.mcl_qscreen_common.restype = C.c_int
+        self.lib.mcl_qscreen_common.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+        if self.lib.mcl_qscreen_common(self.h, _p(a), _p(b), _p(am), len(a), int(q), _p(out)) != 0:
+            raise MCError("mcl_qscreen_common: pair id out of range")
         return out
 
     def run(self, engine, args=(), upload=True, clstr=None, comm=None):

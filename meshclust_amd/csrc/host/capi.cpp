@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "qscreen.hpp"
 #include "runner.hpp"
 
 extern "C" {
@@ -144,6 +145,18 @@ int mcl_label_identities(void *dsv, mc_ctx *ctx, const uint32_t *a, const uint32
     if (err && errcap > 0) snprintf(err, errcap, "%s", e.what());
     return 1;
   }
+}
+
+// qscreen::common (host/qscreen.hpp) of the m pairs, the host twin of mc_qgram_common: common[i] =
+// the q-gram intersection of read a[i] (its minus-strand string where a_minus[i] != 0; NULL: all
+// plus) and read b[i], MC_QGRAM_NA where not available.  Returns 0, or 1 for an id out of range.
+int mcl_qscreen_common(void *dsv, const uint32_t *a, const uint32_t *b, const uint8_t *a_minus, uint64_t m, int q,
+                       uint32_t *common) {
+  const auto *ds = (const mc::Dataset *)dsv;
+  for (uint64_t i = 0; i < m; i++)
+    if (a[i] >= ds->size() || b[i] >= ds->size()) return 1;
+  for (uint64_t i = 0; i < m; i++) common[i] = mc::qscreen::common(*ds, a[i], b[i], a_minus && a_minus[i], q);
+  return 0;
 }
 
 int mcl_run(void *dsv, mc_ctx *ctx, int argc, char **argv, int upload, const char *clstr_path, char *stats,

@@ -20,6 +20,8 @@ int mc_kmer_build_strands(mc_ctx *, int, int, int) __attribute__((weak));
 int mc_orient_pairs(mc_ctx *, const uint32_t *, const uint32_t *, uint64_t, uint8_t *, uint64_t *) __attribute__((weak));
 int mc_nw_identity_strands(mc_ctx *, const uint32_t *, const uint32_t *, const uint8_t *, uint64_t, double *, int32_t *,
                            int32_t *) __attribute__((weak));
+// (the search's q-gram screen counts on the host where the engine has no mc_qgram_common)
+int mc_qgram_common(mc_ctx *, const uint32_t *, const uint32_t *, const uint8_t *, uint64_t, int, uint32_t *) __attribute__((weak));
 }
 
 namespace mc {

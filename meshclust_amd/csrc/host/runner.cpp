@@ -393,6 +393,7 @@ RunResult run_pipeline(const Dataset &ds, mc_ctx *ctx, Options opt, bool upload,
   rr.part = mean_shift_cluster(ds, ctx, *bvp, cc, rr.timer, rr.stats);
   rr.stats.nw_pairs = tr.nw_pairs;
   rr.stats.nw_cells = tr.nw_cells;
+  rr.stats.nw_screened = tr.nw_screened;
   if (opt.both_strands) {
     // every member against its centre, grouped by centre (one staged centre row per cluster)
     Scope s(rr.timer, "orient");
@@ -426,10 +427,10 @@ std::string stats_json(const RunResult &rr, double parse_ms, double write_ms) {
   o += b;
   snprintf(b, sizeof b,
            ", \"scan_steps\": %llu, \"scan_candidates\": %llu, \"update_evals\": %llu, \"merge_evals\": %llu"
-           ", \"nw_pairs\": %llu, \"nw_cells\": %llu, \"align_nw_pairs\": %llu, \"align_nw_cells\": %llu",
+           ", \"nw_pairs\": %llu, \"nw_cells\": %llu, \"nw_screened\": %llu, \"align_nw_pairs\": %llu, \"align_nw_cells\": %llu",
            (unsigned long long)rr.stats.scan_steps, (unsigned long long)rr.stats.scan_candidates,
            (unsigned long long)rr.stats.update_evals, (unsigned long long)rr.stats.merge_evals,
-           (unsigned long long)rr.stats.nw_pairs, (unsigned long long)rr.stats.nw_cells,
+           (unsigned long long)rr.stats.nw_pairs, (unsigned long long)rr.stats.nw_cells, (unsigned long long)rr.stats.nw_screened,
            (unsigned long long)rr.stats.align_nw_pairs, (unsigned long long)rr.stats.align_nw_cells);
   o += b;
   if (rr.strands != 1) {

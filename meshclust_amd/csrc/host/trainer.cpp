@@ -2,6 +2,7 @@
 #include "trainer.hpp"
 
 #include "lazysort.hpp"  // (the two full sorts; the per-pivot sorts are on the device)
+#include "qscreen.hpp"
 
 #include <algorithm>
 #include <array>
@@ -111,6 +112,32 @@ void Trainer::nw_batch(const std::vector<PairId> &pairs, std::vector<double> &id
   check(mc_nw_identity_strands(ctx_, a.data(), b.data(), minus.data(), 2 * m, both.data(), nullptr, nullptr),
         "mc_nw_identity_strands");
   for (size_t i = 0; i < m; i++) ident[i] = both[m + i] > both[i] ? both[m + i] : both[i];
+}
+
+// The q-gram screen of the search's planned pairs (qscreen.hpp): out[i] = 1 where the bound proves
+// pair i below the cutoff -- with both strands, in both orientations.
+void Trainer::screen(const std::vector<PairId> &pairs, int q, bool host, std::vector<char> &out) {
+  const size_t m = pairs.size(), S = cfg_.both_strands ? 2 : 1;
+  out.assign(m, 0);
+  if (m == 0) return;
+  std::vector<uint32_t> cnt(S * m, qscreen::NA);
+  if (host) {
+#pragma omp parallel for schedule(static) num_threads(cfg_.threads)
+    for (size_t j = 0; j < S * m; j++) cnt[j] = qscreen::common(ds_, pairs[j % m].first, pairs[j % m].second, j >= m, q);
+  } else {
+    std::vector<uint32_t> a(S * m), b(S * m);
+    std::vector<uint8_t> minus(S * m, 0);
+    for (size_t j = 0; j < S * m; j++) {
+      a[j] = pairs[j % m].first;
+      b[j] = pairs[j % m].second;
+      minus[j] = j >= m;
+    }
+    check(mc_qgram_common(ctx_, a.data(), b.data(), S == 2 ? minus.data() : nullptr, S * m, q, cnt.data()), "mc_qgram_common");
+  }
+  for (size_t i = 0; i < m; i++) {
+    const uint64_t la = ds_.lengths[pairs[i].first], lb = ds_.lengths[pairs[i].second];
+    out[i] = qscreen::below(cnt[i], la, lb, cfg_.cutoff, q) && (S == 1 || qscreen::below(cnt[m + i], la, lb, cfg_.cutoff, q));
+  }
 }
 
 // Header order of pair ids (the reference's std::set<pair<Point*, Point*>> comparators order
@@ -242,11 +269,11 @@ std::vector<PairId> Trainer::split() {
   // (9 rounds of 450 pairs in the latency form instead of 16 of 150).  With long reads a round
   // is bound by its cells, not by its fixed costs, and the branch not taken is a third of them:
   // one level per round (E9100's search 210 ms against 239, with nw.hip's 8-row chained blocks).
-  // MC_NW_LOOKAHEAD = 1..4 forces it.
+  // MC_NW_LOOKAHEAD = 1..7 forces it.
   const int look = [&] {
     const char *e = getenv("MC_NW_LOOKAHEAD");
     const int v = e ? atoi(e) : long_reads ? 1 : 2;
-    return v < 1 ? 1 : v > 4 ? 4 : v;
+    return v < 1 ? 1 : v > 7 ? 7 : v;
   }();
   // The first round aligns each chain's whole "left spine" -- the pivots the search visits while
   // every identity stays below the cutoff (N/2, N/4, N/8, ...) -- in one batch (MC_NW_SPINE=0/1
@@ -305,19 +332,58 @@ std::vector<PairId> Trainer::split() {
   const int W = cfg_.comm && cfg_.comm->world > 1 ? cfg_.comm->world : 1;
   const size_t per = (P + (size_t)W - 1) / (size_t)W;
   const size_t i0 = std::min(P, per * (size_t)(W > 1 ? cfg_.comm->rank : 0)), i1 = std::min(P, i0 + per);
-  // The spine round aligns the first L levels of every chain, L = 2,048 / chains: the NW
-  // throughput form holds 2,048 waves at once on MI355X (256 CUs x 4 SIMDs x 2 waves of 256
-  // registers), and a batch one wave larger runs a second, mostly empty generation.  Config B's
-  // 150 chains: 13 of ~15 levels, 1,950 pairs; the search 4.9-5.9 -> 4.2 ms
-  // (profiles/r06/ab/spine_levels.txt).  The deeper levels go to the next rounds (identical
-  // pivots either way).  MC_NW_SPINE_LEVELS = L forces L.
+  // The screen (host/qscreen.hpp): after a round's positions are resolved, every
+  // planned pair's q-gram intersection is counted in one call (mc_qgram_common where the engine has
+  // it, the host count otherwise) and a pair the bound proves below the cutoff takes that branch with
+  // no alignment.  The reads left of a pivot's own cluster are unrelated to it, so the "left" levels
+  // of every chain cost a count instead of a 10^6-cell alignment.  MC_NW_SCREEN=0: off;
+  // MC_NW_SCREEN=host: the host count.  With both strands a pair is screened only if both
+  // orientations are.
+  const int screen_q = [&] {
+    const char *e = getenv("MC_NW_SCREEN");
+    if (e && !strcmp(e, "0")) return 0;
+    return qscreen::pick_q(cfg_.cutoff);
+  }();
+  const bool screen_host = [&] {
+    const char *e = getenv("MC_NW_SCREEN");
+    return !mc_qgram_common || (e && !strcmp(e, "host"));
+  }();
+  // The spine round aligns, per chain, the first A = 2,048 / chains of its spine nodes that the
+  // screen leaves: the NW throughput form holds 2,048 waves at once on MI355X (256 CUs x 4 SIMDs x
+  // 2 waves of 256 registers), and a batch one wave larger runs a second, mostly empty generation
+  // (config B's 150 chains: 13; profiles/r06/ab/spine_levels.txt).  With the screen on it plans
+  // every level -- the screened ones cost no alignment -- and with the screen off, or where it
+  // decides nothing, the batch is the first A levels as before.  MC_NW_SPINE_LEVELS = L plans the
+  // first L levels only; MC_NW_SPINE_ALIGN = A forces A.
+  const int spine_gen = (int)std::max<size_t>(1, 2048 / (i1 > i0 ? i1 - i0 : 1));
   const int spine_levels = [&] {
     const char *e = getenv("MC_NW_SPINE_LEVELS");
     const int v = e ? atoi(e) : 0;
-    if (v > 0) return v;
-    const size_t chains = i1 > i0 ? i1 - i0 : 1;
-    return (int)std::max<size_t>(1, 2048 / chains);
+    return v > 0 ? v : screen_q ? 64 : spine_gen;
   }();
+  const int spine_align = [&] {
+    const char *e = getenv("MC_NW_SPINE_ALIGN");
+    const int v = e ? atoi(e) : 0;
+    return v > 0 ? v : spine_gen;
+  }();
+  // Where the screen decides the spine round's first node of at least half the chains it has power
+  // on this input (`decisive`): the reads it leaves are as a rule the pivot's own cluster, above the
+  // cutoff.  Then (a) the spine round aligns nothing: it takes every chain through its screened
+  // prefix for a select and a count, and the next round starts at the first node the screen left;
+  // (b) a round plans `look_deep` levels, whose screened nodes are free, and (c) of an unscreened
+  // node's children only the right one is aligned ahead (MC_NW_SPECULATE=0: both).  A node that is
+  // below the cutoff although the screen left it just ends its chain's walk for the round at its
+  // left child, as any node not aligned does.  With long reads the spine round runs too, for the
+  // screen alone, and the rounds keep one level each.  Config B: the search's NW
+  // launches 3 -> 1, the search 4.2 -> 2.7 ms; 5 levels is the least depth that leaves one launch
+  // (3 and 4: two launches, 3.1-3.2 ms; 6 and 7: as 5; both children: 4.2 ms).
+  const bool screen_spine = screen_q && !(getenv("MC_NW_SPINE") && atoi(getenv("MC_NW_SPINE")) == 0);
+  const int look_deep = [&] {
+    const char *e = getenv("MC_NW_LOOKAHEAD");
+    return e || long_reads ? look : 5;
+  }();
+  const bool speculate = !(getenv("MC_NW_SPECULATE") && atoi(getenv("MC_NW_SPECULATE")) == 0);
+  bool decisive = false;
   auto left_spine = [&](size_t p, size_t o, Plan &pl) {  // every level, identity below the cutoff
     pl.pos.clear();
     pl.kid.clear();
@@ -328,7 +394,7 @@ std::vector<PairId> Trainer::split() {
       p -= o;
     }
   };
-  const uint64_t nw_pairs0 = nw_pairs, nw_cells0 = nw_cells;
+  const uint64_t nw_pairs0 = nw_pairs, nw_cells0 = nw_cells, nw_screened0 = nw_screened;
   {
     Scope s(timer_, "train.sort_keys");
     Scope s3(timer_, "train.sort_keys.pivots");
@@ -364,8 +430,10 @@ std::vector<PairId> Trainer::split() {
   };
   {
     Scope s(timer_, "train.nw_search");
-    std::vector<PairId> batch;
-    std::vector<size_t> who, first;  // chain of each batch entry's tree; first entry of each chain
+    std::vector<PairId> planned, batch;
+    std::vector<size_t> who, first;  // chain of each planned entry's tree; first entry of each chain
+    std::vector<char> scr;           // planned entry: proved below the cutoff
+    std::vector<int> slot;           // planned entry: its place in the NW batch, -1 when not aligned
     std::vector<Plan> plan(P);
     for (int round = 0;; round++) {
       who.clear();
@@ -373,6 +441,7 @@ std::vector<PairId> Trainer::split() {
         if (active[i] && offset[i] == 0) active[i] = 0;
         if (active[i]) who.push_back(i);
       }
+      const bool spine_round = round == 0 && (spine || screen_spine);
       {
         Scope s2(timer_, "train.nw_search.resolve");
         first.assign(who.size() + 1, 0);
@@ -380,8 +449,8 @@ std::vector<PairId> Trainer::split() {
         q_pos.clear();
         for (size_t t = 0; t < who.size(); t++) {
           const size_t i = who[t];
-          if (round == 0 && spine) left_spine(pivot[i], offset[i], plan[i]);
-          else tree(pivot[i], offset[i], look, plan[i]);
+          if (spine_round) left_spine(pivot[i], offset[i], plan[i]);
+          else tree(pivot[i], offset[i], decisive ? look_deep : look, plan[i]);
           for (size_t n = 0; n < plan[i].pos.size(); n++) {
             q_arr.push_back((uint32_t)i);
             q_pos.push_back(plan[i].pos[n]);
@@ -389,21 +458,59 @@ std::vector<PairId> Trainer::split() {
           first[t + 1] = q_arr.size();
         }
         select();
-        batch.resize(q_arr.size());
-        for (size_t q = 0; q < q_arr.size(); q++) batch[q] = PairId(indices[q_arr[q]], q_ids[q]);
+        planned.resize(q_arr.size());
+        for (size_t q = 0; q < q_arr.size(); q++) planned[q] = PairId(indices[q_arr[q]], q_ids[q]);
       }
-      if (batch.empty()) break;
-      std::vector<double> al;
+      if (planned.empty()) break;
       {
+        Scope s4(timer_, "train.nw_search.screen");
+        scr.assign(planned.size(), 0);
+        if (screen_q) screen(planned, screen_q, screen_host, scr);
+        if (spine_round) {
+          size_t roots = 0;
+          for (size_t t = 0; t < who.size(); t++) roots += first[t + 1] > first[t] && scr[first[t]];
+          decisive = 2 * roots >= who.size() && roots > 0;
+        }
+        const int round_cap = !spine_round ? 1 << 30 : decisive || !spine ? 0 : spine_align;
+        // the batch: the nodes the walk can reach that the screen leaves.  The root is reached; a
+        // screened node leads to its left child only, any other to both (plan order: parents first)
+        slot.assign(planned.size(), -1);
+        batch.clear();
+        std::vector<char> need;
+        for (size_t t = 0; t < who.size(); t++) {
+          const Plan &pl = plan[who[t]];
+          const size_t f = first[t];
+          need.assign(pl.pos.size(), 0);
+          need[0] = 1;
+          int aligned = 0;
+          for (size_t n = 0; n < pl.pos.size(); n++) {
+            if (!need[n]) continue;
+            if (scr[f + n]) {
+              nw_screened++;
+              if (pl.kid[n][0] >= 0) need[(size_t)pl.kid[n][0]] = 1;
+              continue;
+            }
+            if (aligned >= round_cap) continue;  // (the walk stops here; the next round's root)
+            aligned++;
+            slot[f + n] = (int)batch.size();
+            batch.push_back(planned[f + n]);
+            for (int side = decisive && speculate ? 1 : 0; side < 2; side++)
+              if (pl.kid[n][(size_t)side] >= 0) need[(size_t)pl.kid[n][(size_t)side]] = 1;
+          }
+        }
+      }
+      std::vector<double> al;
+      if (!batch.empty()) {
         Scope s3(timer_, "train.nw_search.align");
         nw_batch(batch, al);
       }
       for (size_t t = 0; t < who.size(); t++) {
-        const size_t i = who[t];
-        const double *val = al.data() + first[t];  // this chain's nodes, in plan order
+        const size_t i = who[t], f = first[t];  // this chain's nodes, in plan order
         for (int n = 0; n >= 0 && active[i];) {
-          const double algn = val[n];
-          if (algn < cfg_.cutoff) {
+          const bool below = scr[f + (size_t)n];
+          if (!below && slot[f + (size_t)n] < 0) break;  // planned, not aligned: the next round starts here
+          const double algn = below ? 0.0 : al[(size_t)slot[f + (size_t)n]];
+          if (below || algn < cfg_.cutoff) {
             pivot[i] -= offset[i];
             n = plan[i].kid[(size_t)n][0];
           } else if (algn > cfg_.cutoff) {
@@ -440,33 +547,36 @@ std::vector<PairId> Trainer::split() {
       bufs[q_arr[q]].push_back(hdr_less(p, x) ? PairId(p, x) : PairId(x, p));
     }
     if (i1 > i0) check(mc_split_end(ctx_), "mc_split_end");
-    // the ranks' pivots and samples: [nw pairs, nw cells, pairs, pivot[i0..i1), pairs (a << 32 | b)]
-    const size_t cap = per * (2 * to_add_each);
-    std::vector<uint64_t> mine(3 + per + cap, 0), all;
+    // the ranks' pivots and samples: [nw pairs, nw cells, pairs, screened, pivot[i0..i1), pairs (a << 32 | b)]
+    const size_t cap = per * (2 * to_add_each), H = 4;
+    std::vector<uint64_t> mine(H + per + cap, 0), all;
     mine[0] = nw_pairs - nw_pairs0;
     mine[1] = nw_cells - nw_cells0;
+    mine[3] = nw_screened - nw_screened0;
     size_t np = 0;
     for (size_t i = i0; i < i1; i++) {
-      mine[3 + (i - i0)] = pivot[i];
-      for (const PairId &pr : bufs[i]) mine[3 + per + np++] = ((uint64_t)pr.first << 32) | pr.second;
+      mine[H + (i - i0)] = pivot[i];
+      for (const PairId &pr : bufs[i]) mine[H + per + np++] = ((uint64_t)pr.first << 32) | pr.second;
     }
     mine[2] = np;
     if (gather(mine, all)) {
       nw_pairs = nw_pairs0;
       nw_cells = nw_cells0;
+      nw_screened = nw_screened0;
       for (int r = 0; r < W; r++) {
         const uint64_t *b = all.data() + (size_t)r * mine.size();
         const size_t r0 = std::min(P, per * (size_t)r), r1 = std::min(P, r0 + per);
         nw_pairs += b[0];
         nw_cells += b[1];
+        nw_screened += b[3];
         for (size_t i = r0; i < r1; i++) {
-          pivot[i] = b[3 + (i - r0)];
+          pivot[i] = b[H + (i - r0)];
           if (r != cfg_.comm->rank) bufs[i].clear();
         }
         if (r == cfg_.comm->rank) continue;
         // (another rank's pairs go to the first pivot of its block: only the union matters)
         for (uint64_t q = 0; q < b[2] && r1 > r0; q++)
-          bufs[r0].push_back(PairId((uint32_t)(b[3 + per + q] >> 32), (uint32_t)b[3 + per + q]));
+          bufs[r0].push_back(PairId((uint32_t)(b[H + per + q] >> 32), (uint32_t)b[H + per + q]));
       }
     }
   }

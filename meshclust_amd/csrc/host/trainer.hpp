@@ -54,6 +54,7 @@ class Trainer {
   std::vector<PairId> split_pairs;
   std::vector<std::pair<PairId, double>> label_pos, label_neg;
   uint64_t nw_pairs = 0, nw_cells = 0;  // work counters (NW cell updates)
+  uint64_t nw_screened = 0;             // split's search: decisions the q-gram screen took with no alignment
 
  private:
   std::vector<PairId> split();
@@ -64,6 +65,7 @@ class Trainer {
   // all-gather of `words` u64 per rank (every rank the same count); false: one rank
   bool gather(const std::vector<uint64_t> &mine, std::vector<uint64_t> &all) const;
   bool hdr_less(uint32_t a, uint32_t b) const;
+  void screen(const std::vector<PairId> &pairs, int q, bool host, std::vector<char> &out);
 
   const Dataset &ds_;
   mc_ctx *ctx_;
