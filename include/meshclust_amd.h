@@ -692,6 +692,46 @@ int mc_nw_msa_sites(mc_ctx *ctx, const uint64_t *site_off /* nt + 1 */, const ui
 int mc_nw_msa_sites_profile(mc_ctx *ctx, double *out /* 1 */, int reset);
 
 /*
+ * TWO ALIGNMENTS OF ONE READ, BASE BY BASE: the evidence that a read copies one centre on its left and
+ * another on its right (a chimera).  mc_nw_msa_crossover works on the plan of the last mc_nw_msa_begin;
+ * x[c] and y[c] are pair indices of its list (pair i is row nt + i of mc_nw_msa_rows) and name two
+ * pairs of the same read, a[x[c]] == a[y[c]]; their centres and their strands may differ.
+ * For a pair p whose read has la bases and u in [0, la), e_p(u) is 1 if base u of the read AS WRITTEN
+ * lies in an '=' column of p's alignment and 0 otherwise: for a pair begun with a_minus != 0, base i
+ * of seq1 as aligned is base la - 1 - i as written; 'X' and 'I' bases have e = 0, 'D' columns hold no
+ * read base, so the sum of e_p is the ids begin reports for p.  With
+ *   D(s) = sum over u < s of (e_x(u) - e_y(u)),   s = 0 .. la
+ * ids_y + D(s) counts the identities of a two-parent model that follows x on the read's bases [0, s)
+ * and y on [s, la).  Candidate c's MC_CROSS_RES values, out[c * MC_CROSS_RES + slot]:
+ *   0, 1   ids_x, ids_y
+ *   2      best_xy = ids_y + max over s of D(s)   (x left of the cut, y right)
+ *   3, 4   the smallest and the largest s attaining that maximum
+ *   5      best_yx = ids_x - min over s of D(s)   (y left, x right)
+ *   6, 7   the smallest and the largest s attaining that minimum
+ * s = 0 and s = la are allowed, so both best values are at least max(ids_x, ids_y); x == y gives
+ * ids, cuts 0 and la; exchanging x and y exchanges slots 0 <-> 1 and (2, 3, 4) <-> (5, 6, 7); a read
+ * of 0 bases gives eight zeros.  All values are integer sums: nothing depends on batching, on the
+ * order of the candidates or on their split over calls.
+ * No plan: MC_ERR_STATE.  nc = 0: MC_OK.  x, y or out NULL with nc > 0, an index >= m, or
+ * a[x[c]] != a[y[c]]: MC_ERR_ARG.  A read longer than MC_CROSS_MAX_READ bases (what two bitmaps in
+ * 64 KiB of LDS hold; the environment variable MC_CROSS_MAX=<bases>, read per call, lowers it):
+ * MC_ERR_UNSUPPORTED.  All of these are found before any launch, and nothing is written.  The plan is
+ * unchanged and nothing is aligned again: the entry may be mixed freely with rows, counts, sites and
+ * the other alignment entries, and the band mode (mc_set_align_band) changes nothing.
+ * Device: the candidates go in batches of at most MC_CROSS_BATCH_CANDS (MC_CROSS_BATCH=<n> lowers it),
+ * within a batch in launches by read length (at most 1024 << g bases, g = 0 .. 8), each with the LDS
+ * its own longest read needs.  A wavefront per candidate fills two bitmaps of la bits in LDS from the
+ * plan's operation words and scans their difference; 32 bytes per candidate come back.  Timed as
+ * "nw".  mc_nw_msa_crossover_profile: out[0] = device ms of this kernel since the last reset; the
+ * other msa profile entries' values do not include it.
+ */
+#define MC_CROSS_RES 8
+#define MC_CROSS_MAX_READ (1u << 18)
+#define MC_CROSS_BATCH_CANDS (1ull << 20)
+int mc_nw_msa_crossover(mc_ctx *ctx, const uint64_t *x, const uint64_t *y, uint64_t nc, int32_t *out /* nc * MC_CROSS_RES */);
+int mc_nw_msa_crossover_profile(mc_ctx *ctx, double *out /* 1 */, int reset);
+
+/*
  * Accumulation (ClusterFactory::accumulate, ClusterFactory.cpp:637-714).
  * The bvec of Runner.cpp:342-350 is only ever shrunk after insert_finalize, so the device
  * holds one static candidate order (bin-major, length-sorted within bins) plus an alive

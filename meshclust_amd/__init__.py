@@ -36,6 +36,7 @@ CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # MC_CIGAR_*: mc_nw_align_stra
 PILEUP_CH = 8  # MC_PILEUP_CH: counters per row of mc_nw_pileup_strands' table
 MSA_GAP = ord("-")  # MC_MSA_GAP: the gap byte of mc_nw_msa_rows
 MSA_CH = 8  # MC_MSA_CH: counters per column of mc_nw_msa_counts
+CROSS_RES = 8  # MC_CROSS_RES: values per candidate of mc_nw_msa_crossover
 QUAL_MAX = 93  # MC_QUAL_MAX: the largest Phred value mc_load_qualities takes
 QGRAM_NA = 0xFFFFFFFF  # MC_QGRAM_NA: mc_qgram_common's "not available"
 FAMILIES = ("kmer", "keys", "pairs", "scan", "finalize", "mean_shift", "nw", "layout")
@@ -151,6 +152,10 @@ def gpu_lib():
                                         C.c_void_p]
         lib.mc_nw_msa_sites_profile.restype = C.c_int
         lib.mc_nw_msa_sites_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.mc_nw_msa_crossover.restype = C.c_int
+        lib.mc_nw_msa_crossover.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.mc_nw_msa_crossover_profile.restype = C.c_int
+        lib.mc_nw_msa_crossover_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         for name in ("mc_set_align_band", "mc_nw_band_plan", "mc_nw_band_profile"):
             getattr(lib, name).restype = C.c_int
         lib.mc_set_align_band.argtypes = [C.c_void_p, C.c_int]
@@ -257,6 +262,8 @@ def host_lib():
         lib.mcl_assign_variants.restype = C.c_int
         lib.mcl_assign_variants.argtypes = lib.mcl_assign_band.argtypes[:-2] + [C.c_char_p, C.c_char_p, C.c_char_p, C.c_double,
                                                                                 C.c_longlong, C.c_char_p, C.c_int]
+        lib.mcl_assign_chimeras.restype = C.c_int
+        lib.mcl_assign_chimeras.argtypes = lib.mcl_assign_variants.argtypes[:-2] + [C.c_char_p, C.c_longlong, C.c_char_p, C.c_int]
         _host = lib
     return _host
 
@@ -856,6 +863,25 @@ class Engine:
         self._ck(self.lib.mc_nw_msa_sites_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_msa_sites_profile")
         return float(out[0])
 
+    def nw_msa_crossover(self, x, y):
+        """mc_nw_msa_crossover: for candidates (x[c], y[c]), two pairs of the plan that align the same read,
+        -> (nc, CROSS_RES) int32: ids_x, ids_y, best_xy (x left of the cut, y right) with its smallest and
+        largest cut, best_yx (y left, x right) with its smallest and largest cut.  Cuts are positions in
+        the read as written, 0 .. its length."""
+        x = np.ascontiguousarray(x, np.uint64)
+        y = np.ascontiguousarray(y, np.uint64)
+        if x.shape != y.shape or x.ndim != 1:
+            raise ValueError("nw_msa_crossover: x and y are two lists of one length")
+        out = np.zeros((len(x), CROSS_RES), np.int32)
+        self._ck(self.lib.mc_nw_msa_crossover(self.ctx, _p(x), _p(y), C.c_uint64(len(x)), _p(out)), "mc_nw_msa_crossover")
+        return out
+
+    def nw_msa_crossover_profile(self, reset=False):
+        """mc_nw_msa_crossover_profile -> device ms of nw_msa_crossover's kernel since the last reset."""
+        out = np.zeros(1)
+        self._ck(self.lib.mc_nw_msa_crossover_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_msa_crossover_profile")
+        return float(out[0])
+
     def nw_identity_raw(self, a_cat, a_off, b_cat, b_off):
         a_cat = np.ascontiguousarray(a_cat, np.uint8)
         b_cat = np.ascontiguousarray(b_cat, np.uint8)
@@ -882,7 +908,8 @@ class Engine:
 
 def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8, both_strands=False, top=None, hits=None,
                  identity=False, min_identity=None, paf=None, consensus=None, pileup=None, quality=False, msa=None, profile=None,
-                 band=False, variants=None, alleles=None, haplotypes=None, min_allele_frac=0.2, min_allele_count=2):
+                 band=False, variants=None, alleles=None, haplotypes=None, min_allele_frac=0.2, min_allele_count=2,
+                 chimeras=None, min_chimera_gain=3):
     """Place the reads of the FASTA or FASTQ file(s) ``reads`` into the clustering saved by
     ``meshclust --save-model model --save-centres centres`` (mcl_assign: mc_assign on the
     engine's GPU).  Writes the TSV ``out`` (read, centre or *, cluster index or -1, combo 0,
@@ -928,14 +955,28 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     assigned read with its characters at its centre's sites (mc_nw_msa_sites; with ``quality`` their weights too),
     and per centre with a site its distinct allele strings: centre, rank, count, depth, alleles.  ``quality`` and
     ``band`` are accepted beside any of the three.  The stats gain, last, ``variant_centres``, ``variant_sites``,
-    ``allele_bytes`` and the ``variants`` phase."""
+    ``allele_bytes`` and the ``variants`` phase.
+    ``chimeras``: meshclust-assign's --chimeras FILE (mcl_assign_chimeras; needs ``top`` of 2 or more, implies
+    ``identity``): after every other output, every read's hits are aligned again in plans of their own and its best
+    hit is compared with every later hit of another centre (mc_nw_msa_crossover): one line per read with such a hit
+    -- read, left_centre, right_centre, left_strand, right_strand, cut_first, cut_last, ids_left, ids_right, best, gain,
+    read_len, flag -- for the second parent of largest gain; flag is Y where the gain is ``min_chimera_gain`` or more
+    (default 3: a convention, not tuned on real data).  ``band`` is accepted beside it.  The stats gain, last,
+    ``chimera_candidates``, ``chimeras`` and the ``chimeras`` phase."""
     import json
     lib = host_lib()
     files = [reads] if isinstance(reads, str) else list(reads)
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     buf = C.create_string_buffer(1 << 14)
     enc = lambda x: x.encode() if x else None
-    if variants is not None or alleles is not None or haplotypes is not None:
+    if chimeras is not None:
+        rc = lib.mcl_assign_chimeras(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
+                                     enc(unassigned), 1 if both_strands else 0, int(top or 0), enc(hits), 1,
+                                     -1.0 if min_identity is None else float(min_identity), enc(paf), enc(consensus), enc(pileup),
+                                     1 if quality else 0, enc(msa), enc(profile), 1 if band else 0, enc(variants), enc(alleles),
+                                     enc(haplotypes), float(min_allele_frac), int(min_allele_count), enc(chimeras),
+                                     int(min_chimera_gain), buf, len(buf))
+    elif variants is not None or alleles is not None or haplotypes is not None:
         rc = lib.mcl_assign_variants(engine.ctx, model.encode(), centres.encode(), arr, len(files), threads, out.encode(),
                                      enc(unassigned), 1 if both_strands else 0, int(top or 0), enc(hits), 1,
                                      -1.0 if min_identity is None else float(min_identity), enc(paf), enc(consensus), enc(pileup),

@@ -813,6 +813,101 @@ int mc_nw_msa_sites_profile(mc_ctx *c, double *out, int reset) {
   return MC_OK;
 }
 
+int mc_nw_msa_crossover(mc_ctx *c, const uint64_t *x, const uint64_t *y, uint64_t nc, int32_t *out) {
+  if (!c || !c->codes.p || !c->msa_on) return MC_ERR_STATE;
+  if (nc == 0) return MC_OK;
+  if (!x || !y || !out) return MC_ERR_ARG;
+  const std::string who = "mc_nw_msa_crossover";
+  const uint64_t m = c->msa_a.size();
+  const uint64_t cap = env_cap("MC_CROSS_MAX", MC_CROSS_MAX_READ);
+  auto length = [&](uint64_t p) { return c->h_seq_off[c->msa_a[p] + 1] - c->h_seq_off[c->msa_a[p]]; };
+  for (uint64_t k = 0; k < nc; k++) {
+    if (x[k] >= m || y[k] >= m) {
+      set_error(who + ": candidate " + std::to_string(k) + " names pair " + std::to_string(std::max(x[k], y[k])) + ", the plan has " +
+                std::to_string(m));
+      return MC_ERR_ARG;
+    }
+    if (c->msa_a[x[k]] != c->msa_a[y[k]]) {
+      set_error(who + ": candidate " + std::to_string(k) + ": pairs " + std::to_string(x[k]) + " and " + std::to_string(y[k]) +
+                " align different reads");
+      return MC_ERR_ARG;
+    }
+  }
+  for (uint64_t k = 0; k < nc; k++)
+    if (length(x[k]) > cap) {
+      set_error(who + ": candidate " + std::to_string(k) + "'s read has " + std::to_string(length(x[k])) + " bases, the limit is " +
+                std::to_string(cap));
+      return MC_ERR_UNSUPPORTED;
+    }
+  MCG_CHECK(hipSetDevice(c->device));
+  // A batch's candidates go by the size of their bitmaps: bucket g holds the reads of at most 1024 << g bases,
+  // one launch per bucket in use with the LDS its own longest read needs.  Every record names its slot
+  // of the batch's output, so the values come back in the caller's order.
+  constexpr uint32_t NBUCKET = 9;  // 1024 << 8 = MC_CROSS_MAX_READ
+  auto bucket = [](uint64_t la) {
+    uint32_t g = 0;
+    while (g + 1 < NBUCKET && la > (1024ull << g)) g++;
+    return g;
+  };
+  const uint64_t per = env_cap("MC_CROSS_BATCH", MC_CROSS_BATCH_CANDS);
+  std::vector<CrossPair> recs;
+  std::vector<uint32_t> order;
+  for (uint64_t i0 = 0; i0 < nc; i0 += per) {
+    const uint64_t nb = std::min(per, nc - i0);
+    uint64_t cnt[NBUCKET + 1] = {0};
+    uint32_t longest[NBUCKET] = {0};
+    for (uint64_t k = 0; k < nb; k++) {
+      const uint64_t la = length(x[i0 + k]);
+      const uint32_t g = bucket(la);
+      cnt[g + 1]++;
+      longest[g] = std::max(longest[g], (uint32_t)la);
+    }
+    for (uint32_t g = 0; g < NBUCKET; g++) cnt[g + 1] += cnt[g];
+    recs.resize(nb);
+    {
+      uint64_t at[NBUCKET];
+      for (uint32_t g = 0; g < NBUCKET; g++) at[g] = cnt[g];
+      for (uint64_t k = 0; k < nb; k++) {
+        const uint64_t px = x[i0 + k], py = y[i0 + k], la = length(px);
+        CrossPair r{};
+        r.xw_off = c->msa_woff[px];
+        r.yw_off = c->msa_woff[py];
+        r.la = (uint32_t)la;
+        r.xnw = c->msa_nops[px];
+        r.ynw = c->msa_nops[py];
+        r.minus = c->msa_minus.empty() ? 0u : (c->msa_minus[px] ? 1u : 0u) | (c->msa_minus[py] ? 2u : 0u);
+        r.out = (uint32_t)k;
+        recs[at[bucket(la)]++] = r;
+      }
+    }
+    TRY(upload(c, c->msa_xrec, recs.data(), recs.size(), c->stream));
+    TRY(ensure(c->msa_xout, nb * MC_CROSS_RES * 4 + 64));
+    for (uint32_t g = 0; g < NBUCKET; g++)
+      TRY(launch_crossover(c, (uint32_t)(cnt[g + 1] - cnt[g]), (const CrossPair *)c->msa_xrec.p + cnt[g], (const uint32_t *)c->msa_words.p,
+                           longest[g], (int32_t *)c->msa_xout.p));
+    const uint64_t bytes = nb * MC_CROSS_RES * 4;
+    uint8_t *h = nullptr;
+    TRY(download_pinned(c, c->msa_xout.p, bytes, c->stream, &h));  // (synchronizes: the records are the next batch's)
+    if (h) {
+      memcpy(out + i0 * MC_CROSS_RES, h, bytes);
+    } else {
+      MCG_CHECK(hipMemcpyAsync(out + i0 * MC_CROSS_RES, c->msa_xout.p, bytes, hipMemcpyDeviceToHost, c->stream));
+      MCG_CHECK(hipStreamSynchronize(c->stream));
+    }
+  }
+  flush_timers(c);
+  return MC_OK;
+}
+
+int mc_nw_msa_crossover_profile(mc_ctx *c, double *out, int reset) {
+  if (!c || !out) return MC_ERR_ARG;
+  (void)hipStreamSynchronize(c->stream);
+  flush_timers(c);
+  out[0] = c->fam_ms[F_NW_CROSS];
+  if (reset) c->fam_ms[F_NW_CROSS] = c->fam_n[F_NW_CROSS] = 0;
+  return MC_OK;
+}
+
 int mc_nw_msa_end(mc_ctx *c) {
   if (!c) return MC_ERR_ARG;
   msa_drop(c);
@@ -820,7 +915,7 @@ int mc_nw_msa_end(mc_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   for (Buf *b : {&c->msa_width, &c->msa_col, &c->msa_words, &c->msa_bw, &c->msa_rec, &c->msa_out, &c->msa_cnt, &c->msa_wcnt,
                  &c->msa_cdiff, &c->msa_crec, &c->msa_ctgt, &c->msa_scol, &c->msa_sres, &c->msa_stgt, &c->msa_srec, &c->msa_sout,
-                 &c->msa_sq}) {
+                 &c->msa_sq, &c->msa_xrec, &c->msa_xout}) {
     if (b->p) (void)hipFree(b->p);
     *b = Buf{};
   }

@@ -34,8 +34,9 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // the width + column kernels and the render kernel of msa.hip, part of F_NW, for mc_nw_msa_profile;
 // F_NW_MSAC: the counts kernels of msa.hip (mc_nw_msa_counts), part of F_NW, for mc_nw_msa_counts_profile;
 // F_NW_BAND: the score-only launches of the width search (nwband.hip), part of F_NW, for mc_nw_band_profile;
-// F_NW_MSAS: the resolve and gather kernels of msa.hip (mc_nw_msa_sites), part of F_NW, for mc_nw_msa_sites_profile
-enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NW_MSAC, F_NW_BAND, F_NW_MSAS, F_NALL };
+// F_NW_MSAS: the resolve and gather kernels of msa.hip (mc_nw_msa_sites), part of F_NW, for mc_nw_msa_sites_profile;
+// F_NW_CROSS: the kernel of crossover.hip (mc_nw_msa_crossover), part of F_NW, for mc_nw_msa_crossover_profile
+enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NW_MSAC, F_NW_BAND, F_NW_MSAS, F_NW_CROSS, F_NALL };
 
 // Classifier in the form the kernels consume (mc_classifier + the exact decision threshold).
 struct DevClassifier {
@@ -158,6 +159,14 @@ struct MsaSitePair {
   uint32_t la, lb, nw, S, a_rc, pad;
 };
 
+// One candidate of a batch of mc_nw_msa_crossover (crossover.hip): the packed words of its two plan
+// pairs x and y, la the bases of the read both have, minus bit 0 / bit 1: x / y was aligned
+// reverse-complemented; its MC_CROSS_RES values go to slot `out` of the batch's output.
+struct CrossPair {
+  uint64_t xw_off, yw_off;
+  uint32_t la, xnw, ynw, minus, out, pad;
+};
+
 // A range of one array of the device lazy introsort (split.hip): partitioned (left >= 0:
 // children left, left + 1, cut between them) or finished (fin: a sorted leaf).
 struct SplitNode {
@@ -269,9 +278,10 @@ struct mc_ctx {
   // msa_scol / msa_sres / msa_stgt / msa_srec / msa_sout / msa_sq: a call's site columns, their
   // resolved (row, slot + 1 or 0) and target records, a gather batch's pair records, alleles and
   // weights (mc_nw_msa_sites only).
+  // msa_xrec / msa_xout: a batch's candidate records and results (mc_nw_msa_crossover only).
   bool msa_on = false;
   mcg::Buf msa_width, msa_col, msa_words, msa_bw, msa_rec, msa_out, msa_cnt, msa_wcnt, msa_cdiff, msa_crec, msa_ctgt;
-  mcg::Buf msa_scol, msa_sres, msa_stgt, msa_srec, msa_sout, msa_sq;
+  mcg::Buf msa_scol, msa_sres, msa_stgt, msa_srec, msa_sout, msa_sq, msa_xrec, msa_xout;
   std::vector<uint32_t> msa_a, msa_b, msa_targets, msa_tof, msa_nops, msa_tp;
   std::vector<uint64_t> msa_tp_off;
   std::vector<uint8_t> msa_minus;
@@ -430,6 +440,9 @@ int launch_msa_sites_resolve(mc_ctx *c, uint32_t nt, const MsaSiteTarget *d_tgts
 int launch_msa_sites(mc_ctx *c, uint64_t npairs, const MsaSitePair *d_pairs, const uint8_t *d_rc, const uint32_t *d_words,
                      const uint32_t *d_width, const uint32_t *d_col, const uint32_t *d_sites, const uint2 *d_res, uint8_t *d_out,
                      uint8_t *d_qout);
+// crossover.hip (mc_nw_msa_crossover): per candidate of d_cands, none with a read above max_la bases, the
+// eight values of its two pairs' '=' bitmaps into d_out; the launch's LDS is two bitmaps of max_la bits.
+int launch_crossover(mc_ctx *c, uint32_t nc, const CrossPair *d_cands, const uint32_t *d_words, uint32_t max_la, int32_t *d_out);
 // abi_align.hip: forget mc_nw_msa_begin's plan (its device buffers stay for the next one)
 void msa_drop(mc_ctx *c);
 

@@ -21,6 +21,7 @@
 #include "revseq.hpp"
 #include "topk.hpp"
 #include "variants.hpp"
+#include "chimera.hpp"
 #include "verify.hpp"
 
 namespace mc {
@@ -29,7 +30,7 @@ static const char *kUsage =
     "Usage: meshclust-assign --model FILE --centres FILE reads.fa [more.fa] --output assign.tsv "
     "[--unassigned rest.fa] [--both-strands] [--top K --hits FILE] [--identity] [--min-identity X] [--paf FILE] [--consensus FILE] "
     "[--pileup FILE] [--quality] [--msa FILE] [--profile FILE] [--band] [--variants FILE] [--alleles FILE] [--haplotypes FILE] [--min-allele-frac X] "
-    "[--min-allele-count N] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
+    "[--min-allele-count N] [--chimeras FILE] [--min-chimera-gain N] [--device N] [--threads N] [--stats-json FILE] [--quiet]\n"
     "  --both-strands  score every read as written and reverse-complemented; the TSV gains a strand column\n"
     "                  (implied by a version-2 model, saved by meshclust --both-strands: reads and centres are then\n"
     "                  scored once on their canonical rows and every hit's strand comes from mc_orient_pairs; with\n"
@@ -58,7 +59,8 @@ static const char *kUsage =
     "  --profile FILE  (implies --identity) that alignment counted per column, for centres with reads: centre, column,\n"
     "                  centre_pos, slot (0: a centre base; from 1: an inserted column before it), base (- inserted),\n"
     "                  depth, A, C, G, T, N, gap; with --quality (FASTQ reads) also wA wC wG wT wN wgap\n"
-    "  --band          (with --paf, --consensus, --pileup, --msa, --profile, --variants, --alleles or --haplotypes) record\n"
+    "  --band          (with --paf, --consensus, --pileup, --msa, --profile, --variants, --alleles, --haplotypes or\n"
+    "                  --chimeras) record\n"
     "                  only a certified band of every alignment's choices (mc_set_align_band): less scratch, more pairs per\n"
     "                  batch, no output file changes\n"
     "  --variants FILE  (implies --identity) the --profile lines of the variant sites of every centre with reads: the\n"
@@ -69,6 +71,14 @@ static const char *kUsage =
     "  --haplotypes FILE  (implies --identity) per centre with a site, one line per distinct allele string seen\n"
     "                  --min-allele-count times or more: centre, rank, count, depth, alleles\n"
     "  --min-allele-frac X  (0 < X <= 1, default 0.2)   --min-allele-count N  (N >= 1, default 2)\n"
+    "  --chimeras FILE  (needs --top K with K >= 2, implies --identity) compare every read's best hit with each later hit\n"
+    "                  of another centre, base by base along the read, and write the second parent that adds most: read,\n"
+    "                  left_centre, right_centre, left_strand, right_strand, cut_first, cut_last (0-based positions in the\n"
+    "                  read as written), ids_left, ids_right, best, gain, read_len, flag\n"
+    "  --min-chimera-gain N  (N >= 1, default 3) flag Y where the two-parent model has N identities or more above the\n"
+    "                  better single parent.  3 is a convention and is not tuned: on error-free planted reads of 120\n"
+    "                  bases from parents 10 % apart the gains were 3 .. 8; with parents 5 % apart and 3 % read error\n"
+    "                  only 2 .. 3, so the flag is weak there.  Real data was not measured\n"
     "  reads and centres may be FASTA or FASTQ files (decided per file); without --quality the qualities are skipped\n";
 
 AssignOptions parse_assign_options(int argc, char **argv) {
@@ -128,6 +138,15 @@ AssignOptions parse_assign_options(int argc, char **argv) {
     } else if (arg == "--haplotypes" && has) {
       o.haplotypes = argv[++i];
       o.identity = true;
+    } else if (arg == "--chimeras" && has) {
+      o.chimeras = argv[++i];
+      o.identity = true;
+    } else if (arg == "--min-chimera-gain" && has) {
+      char *end = nullptr;
+      const char *txt = argv[++i];
+      const long long v = strtoll(txt, &end, 10);
+      if (end == txt || *end || v < 1) throw Error(std::string("--min-chimera-gain must be 1 or more\n") + kUsage, 1);
+      o.min_chimera_gain = v;
     } else if (arg == "--min-allele-frac" && has) {
       char *end = nullptr;
       const char *txt = argv[++i];
@@ -149,9 +168,10 @@ AssignOptions parse_assign_options(int argc, char **argv) {
   if (o.model.empty() || o.centres.empty() || o.reads.empty())
     throw Error(std::string("--model, --centres and at least one reads file are required\n") + kUsage, 1);
   if ((o.top > 0) != !o.hits.empty()) throw Error(std::string("--top K and --hits FILE are given together\n") + kUsage, 1);
+  if (!o.chimeras.empty() && o.top < 2) throw Error(std::string("--chimeras FILE needs --top K with K >= 2\n") + kUsage, 1);
   if (o.quality && o.consensus.empty() && o.pileup.empty() && o.profile.empty() && !o.any_variants())
     throw Error(std::string("--quality needs --consensus FILE and/or --pileup FILE (or --profile FILE)\n") + kUsage, 1);
-  if (o.band && o.paf.empty() && o.consensus.empty() && o.pileup.empty() && o.msa.empty() && o.profile.empty() && !o.any_variants())
+  if (o.band && o.paf.empty() && o.consensus.empty() && o.pileup.empty() && o.msa.empty() && o.profile.empty() && !o.any_variants() && o.chimeras.empty())
     throw Error(std::string("--band needs --paf, --consensus, --pileup, --msa or --profile\n") + kUsage, 1);
   return o;
 }
@@ -663,6 +683,81 @@ static void msa_output(mc_ctx *ctx, const Dataset &ds, uint32_t C, const std::ve
   rest();
 }
 
+// --chimeras: chimera.hpp over the reads' hits (rows of K slots, mc_assign_top's order), in plans of its own.  The
+// reads with a candidate go in ranges whose pairs stay within kPairs; a read's pairs are its first hit and its
+// candidates, the plan's targets the centres among a range's pairs.
+static void chimera_output(mc_ctx *ctx, const Dataset &ds, uint64_t C, uint64_t M, uint32_t K, const std::vector<uint32_t> &hit,
+                           const std::vector<uint8_t> &hit_strand, const AssignOptions &opt, AssignResult &r) {
+  r.chimeras = true;
+  TextFile cf(opt.chimeras);
+  const uint64_t kPairs = 1ull << 18;
+  std::vector<uint32_t> pa, pb, targets, cand(K), rcand;  // rcand: the candidates' hit indices, read after read
+  std::vector<uint8_t> pm;
+  std::vector<uint64_t> x, y, reads, rfirst;  // reads: the range's reads; rfirst: where a read's candidates start
+  std::vector<int32_t> res;
+  char num[160];
+  auto flush = [&]() {
+    if (reads.empty()) return;
+    targets = pb;
+    std::sort(targets.begin(), targets.end());
+    targets.erase(std::unique(targets.begin(), targets.end()), targets.end());
+    const uint32_t nt = (uint32_t)targets.size();
+    std::vector<uint64_t> row_off((size_t)nt + 1), W(nt);
+    check(mc_nw_msa_begin(ctx, pa.data(), pb.data(), pm.data(), pa.size(), targets.data(), nt, row_off.data(), nullptr, W.data(),
+                          nullptr, nullptr, nullptr),
+          "mc_nw_msa_begin");
+    struct End {
+      mc_ctx *c;
+      ~End() { mc_nw_msa_end(c); }
+    } ender{ctx};
+    res.assign(x.size() * MC_CROSS_RES, 0);
+    check(mc_nw_msa_crossover(ctx, x.data(), y.data(), x.size(), res.data()), "mc_nw_msa_crossover");
+    rfirst.push_back(x.size());
+    for (size_t n = 0; n < reads.size(); n++) {
+      const uint64_t q = reads[n], k0 = rfirst[n], k = rfirst[n + 1] - k0;
+      const ChimeraCall c = chimera_pick(rcand.data() + k0, (uint32_t)k, res.data() + k0 * MC_CROSS_RES, opt.min_chimera_gain);
+      const uint64_t h1 = q * K, h2 = q * K + (uint64_t)c.hit, left = c.xy ? h1 : h2, right = c.xy ? h2 : h1;
+      std::string &text = cf.text;
+      text.append(ds.headers[C + q].substr(1));
+      text += '\t';
+      text.append(ds.headers[hit[left]].substr(1));
+      text += '\t';
+      text.append(ds.headers[hit[right]].substr(1));
+      snprintf(num, sizeof num, "\t%c\t%c\t%d\t%d\t%d\t%d\t%d\t%d\t%llu\t%c\n", hit_strand[left] ? '-' : '+',
+               hit_strand[right] ? '-' : '+', c.cut_first, c.cut_last, c.ids_left, c.ids_right, c.best, c.gain,
+               (unsigned long long)ds.lengths[C + q], c.flag ? 'Y' : 'N');
+      text += num;
+      r.chimera_candidates++;
+      if (c.flag) r.chimera_flagged++;
+      cf.flush(false);
+    }
+    pa.clear(), pb.clear(), pm.clear(), x.clear(), y.clear(), reads.clear(), rfirst.clear(), rcand.clear();
+  };
+  for (uint64_t q = 0; q < M; q++) {
+    uint32_t n = 0;
+    while (n < K && hit[q * K + n] != MC_ASSIGN_NONE) n++;
+    const uint32_t k = n ? chimera_candidates(&hit[q * K], n, cand.data()) : 0;
+    if (k == 0) continue;
+    if (!pa.empty() && pa.size() + k + 1 > kPairs) flush();
+    reads.push_back(q);
+    rfirst.push_back(x.size());
+    const uint64_t first = pa.size();
+    for (uint32_t t = 0; t <= k; t++) {  // the first hit, then the candidates
+      const uint32_t j = t ? cand[t - 1] : 0;
+      pa.push_back((uint32_t)(C + q));
+      pb.push_back(hit[q * K + j]);
+      pm.push_back(hit_strand[q * K + j]);
+      if (t) {
+        x.push_back(first);
+        y.push_back(first + t);
+        rcand.push_back(j);
+      }
+    }
+  }
+  flush();
+  cf.close();
+}
+
 AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
   AssignOptions opt = opt_in;
   AssignResult r;
@@ -980,6 +1075,11 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
     const double tail = ms_since(t0) - (r.msa_ms + r.profile_ms + r.variants_ms);
     (r.msa ? r.msa_ms : r.profile ? r.profile_ms : r.variants_ms) += tail;
   }
+  if (!opt.chimeras.empty()) {  // after every other user of the plan: its begins drop theirs
+    t0 = std::chrono::steady_clock::now();
+    chimera_output(ctx, ds, C, M, K, hit, hit_strand, opt, r);
+    r.chimeras_ms = ms_since(t0);
+  }
   t0 = std::chrono::steady_clock::now();
   // one line per read, in input order: read header, centre header or *, cluster index or -1,
   // combo 0, similar centres (headers without their '>'); with both strands a sixth column: the
@@ -1057,7 +1157,7 @@ AssignResult run_assign(mc_ctx *ctx, const AssignOptions &opt_in) {
 std::string assign_stats_json(const AssignResult &r) {
   // (one strand, no --top, no --identity: exactly the keys there were before any of the options)
   char b[2560], s[704] = "", idms[48] = "", msa[224] = "", msams[48] = "", prof[128] = "", profms[48] = "", band[224] = "";
-  char var[192] = "", varms[48] = "";
+  char var[192] = "", varms[48] = "", chim[128] = "", chimms[48] = "";
   int n = 0;
   if (r.strands != MC_STRAND_PLUS)
     n = snprintf(s, sizeof s, "\"strands\": %d, \"assigned_minus\": %llu, ", r.strands, (unsigned long long)r.assigned_minus);
@@ -1096,14 +1196,19 @@ std::string assign_stats_json(const AssignResult &r) {
              (unsigned long long)r.variant_centres, (unsigned long long)r.variant_sites, (unsigned long long)r.allele_bytes);
     snprintf(varms, sizeof varms, ", \"variants\": %.3f", r.variants_ms);
   }
+  if (r.chimeras) {  // after every key there was before --chimeras
+    snprintf(chim, sizeof chim, ", \"chimera_candidates\": %llu, \"chimeras\": %llu", (unsigned long long)r.chimera_candidates,
+             (unsigned long long)r.chimera_flagged);
+    snprintf(chimms, sizeof chimms, ", \"chimeras\": %.3f", r.chimeras_ms);
+  }
   snprintf(b, sizeof b,
            "{\"reads\": %llu, \"centres\": %llu, \"assigned\": %llu, \"unassigned\": %llu, %s\"k\": %d, \"width\": %d, "
            "\"path\": \"%s\", \"candidate_pairs\": %llu, \"fallback_pairs\": %llu, \"device_us\": %llu, "
-           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f%s%s%s}%s%s%s%s}",
+           "\"phases_ms\": {\"parse\": %.3f, \"upload\": %.3f, \"kmer\": %.3f, \"assign\": %.3f, %s\"write\": %.3f%s%s%s%s}%s%s%s%s%s}",
            (unsigned long long)r.reads, (unsigned long long)r.centres, (unsigned long long)r.assigned,
            (unsigned long long)(r.reads - r.assigned), s, r.k, r.width, r.path.c_str(), (unsigned long long)r.candidates,
            (unsigned long long)r.fallbacks, (unsigned long long)r.device_us, r.parse_ms, r.upload_ms, r.kmer_ms,
-           r.assign_ms, idms, r.write_ms, msams, profms, varms, msa, prof, band, var);
+           r.assign_ms, idms, r.write_ms, msams, profms, varms, chimms, msa, prof, band, var, chim);
   return b;
 }
 

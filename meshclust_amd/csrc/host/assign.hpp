@@ -32,6 +32,8 @@ struct AssignOptions {
   double min_allele_frac = 0.2;    // --min-allele-frac X (0 < X <= 1) and --min-allele-count N (N >= 1): variants.hpp's rule
   uint64_t min_allele_count = 2;
   bool any_variants() const { return !variants.empty() || !alleles.empty() || !haplotypes.empty(); }
+  std::string chimeras;       // --chimeras FILE (needs top >= 2, implies identity): every read's best second parent, TSV
+  int64_t min_chimera_gain = 3;  // --min-chimera-gain N (N >= 1): chimera.hpp's flag; 3 is a convention, not tuned
 };
 
 struct AssignResult {
@@ -61,8 +63,10 @@ struct AssignResult {
   uint64_t band_pairs = 0, band_full = 0, band_launches = 0, band_w_sum = 0;
   bool variants = false;         // --variants / --alleles / --haplotypes: centres with a site, their sites, bytes of mc_nw_msa_sites
   uint64_t variant_centres = 0, variant_sites = 0, allele_bytes = 0;
+  bool chimeras = false;         // --chimeras: reads with a second-parent candidate (lines written), those flagged Y
+  uint64_t chimera_candidates = 0, chimera_flagged = 0;
   std::string path;  // "device" (mc_assign) or "pairs" (mc_classify_pairs batches)
-  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0, msa_ms = 0, profile_ms = 0, variants_ms = 0;
+  double parse_ms = 0, upload_ms = 0, kmer_ms = 0, assign_ms = 0, identity_ms = 0, write_ms = 0, msa_ms = 0, profile_ms = 0, variants_ms = 0, chimeras_ms = 0;
 };
 
 // Throws mc::Error (bad options: code 1 with the usage text in what()).
@@ -137,7 +141,18 @@ AssignOptions parse_assign_options(int argc, char **argv);
 // bytes: centre, rank (from 1), count, depth, alleles.  The stats gain, after every other key, "variant_centres"
 // (centres with a site), "variant_sites" and "allele_bytes" (the bytes mc_nw_msa_sites returned), and the phases
 // "variants".
-// With band (it needs paf, consensus, pileup, msa, profile, variants, alleles or haplotypes: parse_assign_options, usage error) the context is
+// With chimeras (it needs top >= 2: parse_assign_options, usage error; implies identity; changes no other output) a
+// phase of its own runs after every other user of mc_nw_msa_begin's plan, because its begins drop theirs.  The reads
+// with a candidate second parent (chimera.hpp: a hit after the first whose centre differs from the first hit's) go in
+// input order in ranges whose pairs stay within 2^18 (a read's pairs together); a range's pairs are those reads'
+// first hit and candidate hits on the hits' strands, its targets the centres among them, through one
+// mc_nw_msa_begin and one mc_nw_msa_crossover of (first hit, candidate) per candidate.  chimeras gets one line per
+// such read: read, left_centre, right_centre, left_strand, right_strand (+ or -), cut_first, cut_last (0-based
+// positions in the read as written: the right parent starts there), ids_left, ids_right (the single parents'
+// identities), best, gain, read_len, flag (Y where gain >= min_chimera_gain, else N) for the candidate chimera_pick
+// chooses.  The stats gain, after every other key, "chimera_candidates" (the lines) and "chimeras" (those flagged
+// Y), and the phases "chimeras".
+// With band (it needs paf, consensus, pileup, msa, profile, variants, alleles, haplotypes or chimeras: parse_assign_options, usage error) the context is
 // set to mc_set_align_band 1 for the run and back to 0 at its end: every alignment pass plans a width per pair
 // and records the certified band alone.  No output file changes.  The stats gain, after every other key,
 // "band_pairs", "band_full", "band_launches" and "band_w_sum" (mc_nw_band_profile over the run).

@@ -18,6 +18,8 @@ struct VariantArgs {  // mcl_assign_variants' own arguments; the defaults are "n
   const char *variants = nullptr, *alleles = nullptr, *haplotypes = nullptr;
   double min_allele_frac = 0.2;
   long long min_allele_count = 2;
+  const char *chimeras = nullptr;  // mcl_assign_chimeras' own
+  long long min_chimera_gain = 3;
 };
 
 static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads,
@@ -34,6 +36,9 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
       throw mc::Error("mcl_assign_variants: min_allele_frac is above 0 and at most 1, min_allele_count 1 or more", 1);
     opt.min_allele_frac = va.min_allele_frac;
     opt.min_allele_count = (uint64_t)va.min_allele_count;
+    if (va.chimeras) opt.chimeras = va.chimeras;
+    if (va.min_chimera_gain < 1) throw mc::Error("mcl_assign_chimeras: min_chimera_gain is 1 or more", 1);
+    opt.min_chimera_gain = va.min_chimera_gain;
     opt.quality = quality;
     opt.band = band;
     if (msa) opt.msa = msa;
@@ -48,7 +53,7 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
       throw mc::Error("mcl_assign_top: top (1 .. MC_ASSIGN_MAX_TOP) and hits are given together", 1);
     if (!(min_identity <= 1)) throw mc::Error("mcl_assign_identity: min_identity is 0 .. 1 (negative: off)", 1);
     opt.min_identity = min_identity < 0 ? -1 : min_identity;
-    opt.identity = identity != 0 || min_identity >= 0 || !opt.paf.empty() || !opt.consensus.empty() || !opt.pileup.empty() || !opt.msa.empty() || !opt.profile.empty() || opt.any_variants();
+    opt.identity = identity != 0 || min_identity >= 0 || !opt.paf.empty() || !opt.consensus.empty() || !opt.pileup.empty() || !opt.msa.empty() || !opt.profile.empty() || opt.any_variants() || !opt.chimeras.empty();
     opt.model = model ? model : "";
     opt.centres = centres ? centres : "";
     for (int i = 0; i < nreads; i++) opt.reads.push_back(reads[i]);
@@ -59,7 +64,9 @@ static int assign_entry(mc_ctx *ctx, const char *model, const char *centres, con
     if (opt.model.empty() || opt.centres.empty() || opt.reads.empty()) throw mc::Error("mcl_assign: model, centres and reads are required", 1);
     if (quality && opt.consensus.empty() && opt.pileup.empty() && opt.profile.empty() && !opt.any_variants())
       throw mc::Error("mcl_assign_qconsensus: quality needs consensus and/or pileup (or profile)", 1);
-    if (band && opt.paf.empty() && opt.consensus.empty() && opt.pileup.empty() && opt.msa.empty() && opt.profile.empty() && !opt.any_variants())
+    if (!opt.chimeras.empty() && top < 2) throw mc::Error("mcl_assign_chimeras: chimeras needs top of 2 or more (and hits)", 1);
+    if (band && opt.paf.empty() && opt.consensus.empty() && opt.pileup.empty() && opt.msa.empty() && opt.profile.empty() && !opt.any_variants() &&
+        opt.chimeras.empty())
       throw mc::Error("mcl_assign_band: band needs paf, consensus, pileup, msa or profile", 1);
     const mc::AssignResult r = mc::run_assign(ctx, opt);
     if (stats && cap > 0) snprintf(stats, cap, "%s", mc::assign_stats_json(r).c_str());
@@ -199,6 +206,29 @@ int mcl_assign_variants(mc_ctx *ctx, const char *model, const char *centres, con
   va.haplotypes = haplotypes;
   va.min_allele_frac = min_allele_frac;
   va.min_allele_count = min_allele_count;
+  return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
+                      min_identity, paf, consensus, pileup, quality != 0, msa, profile, band != 0, stats, cap, va);
+}
+
+// mcl_assign_variants with meshclust-assign's --chimeras `chimeras` (mc_nw_msa_crossover and chimera.hpp over every
+// read's hits, in plans of its own after every other output; needs top of 2 or more, implies identity, may be NULL)
+// at --min-chimera-gain `min_chimera_gain` (1 or more): one line per read with a candidate second parent; band is
+// then accepted beside it.  The summary gains, after every other key, "chimera_candidates", "chimeras" and the
+// "chimeras" phase.  chimeras NULL (at any valid gain; the default is 3) is mcl_assign_variants.
+int mcl_assign_chimeras(mc_ctx *ctx, const char *model, const char *centres, const char *const *reads, int nreads, int threads,
+                        const char *tsv, const char *unassigned, int both_strands, int top, const char *hits, int identity,
+                        double min_identity, const char *paf, const char *consensus, const char *pileup, int quality, const char *msa,
+                        const char *profile, int band, const char *variants, const char *alleles, const char *haplotypes,
+                        double min_allele_frac, long long min_allele_count, const char *chimeras, long long min_chimera_gain,
+                        char *stats, int cap) {
+  VariantArgs va;
+  va.variants = variants;
+  va.alleles = alleles;
+  va.haplotypes = haplotypes;
+  va.min_allele_frac = min_allele_frac;
+  va.min_allele_count = min_allele_count;
+  va.chimeras = chimeras;
+  va.min_chimera_gain = min_chimera_gain;
   return assign_entry(ctx, model, centres, reads, nreads, threads, tsv, unassigned, both_strands != 0, top, hits, identity,
                       min_identity, paf, consensus, pileup, quality != 0, msa, profile, band != 0, stats, cap, va);
 }
