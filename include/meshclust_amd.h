@@ -732,6 +732,48 @@ int mc_nw_msa_crossover(mc_ctx *ctx, const uint64_t *x, const uint64_t *y, uint6
 int mc_nw_msa_crossover_profile(mc_ctx *ctx, double *out /* 1 */, int reset);
 
 /*
+ * DEREPLICATION.  Two points are DUPLICATES if their expanded byte strings (what mc_nw_identity reads:
+ * 0..3 inside segments, 'N' or the raw upper-case byte outside) are equal; with both strands also if
+ * one string equals the other's minus-strand string (above).  The map of the minus strand is an
+ * involution, so this is an equivalence relation and comparing against one member of a class decides
+ * membership.  The bytes decide, not the letters: a record kept as raw letters and the same bases as
+ * digits are not duplicates (lower case is folded by the parser before anything is loaded).
+ * mc_derep, for the m points ids (an id may occur more than once: the occurrences are duplicates of
+ * each other; two empty strings are duplicates):
+ *   rep[i]    the smallest position j of the list such that point ids[j] is a duplicate of point
+ *             ids[i]; so rep[rep[i]] == rep[i] and rep[i] == i for a class's first member
+ *   minus[i]  0 where ids[i]'s string equals that of ids[rep[i]] as written -- this wins, so a string
+ *             that is its own minus strand gives 0 --, else 1: it equals the representative's
+ *             minus-strand string.  With strands == MC_STRAND_PLUS minus may be NULL and is all zeros.
+ * The result is exact and a function of the strings alone: it does not depend on where a string lies
+ * in the buffer, on the order of ids beyond the rule of the smallest position, on batching, on the grid
+ * or on the fingerprint function; no hash collision can merge or split a class.
+ * Device (gpu/derep.hip): one fingerprint kernel over the listed points, a wavefront
+ * per point, gives every point a 128-bit key, a position-keyed integer sum of its bytes with the
+ * length mixed in; with both strands the key is the smaller of the string's and its minus strand's,
+ * both from the same loads.  The host sorts the positions by (key, length, position); a run of equal
+ * (key, length) is a candidate group, its first position the leader.  The compare kernel, a wavefront
+ * per pair, returns for every other member a byte: bit 0 equal to the leader as written, bit 1 equal
+ * to the leader's minus-strand string.  Members that match neither way (a collision of keys) form a
+ * new group under their own first position and are compared again, until none is left; every round
+ * settles at least the leader of every open group.  The pairs of a round go in batches of
+ * MC_DEREP_BATCH_PAIRS.  Environment, read per call: MC_DEREP_BATCH=<pairs> lowers the batch,
+ * MC_DEREP_HASH_BITS=<0..128> keeps only that many leading bits of every key (0: all points of one
+ * length form one group) -- the test hook of the collision rounds; neither changes a result.
+ * No sequences: MC_ERR_STATE.  strands other than MC_STRAND_PLUS or MC_STRAND_PLUS | MC_STRAND_MINUS,
+ * an id >= n, ids or rep NULL with m > 0, minus NULL with both strands, m >= 2^32: MC_ERR_ARG.  m = 0:
+ * MC_OK.  All of these are found before any launch; rep and minus are written only by a call that
+ * returns MC_OK.  There is no host fallback.
+ * mc_derep_profile, since the last reset: out[0] device ms of the fingerprint kernel, out[1] device ms
+ * of the compare kernel, out[2] pairs compared, out[3] compare rounds, out[4] pairs whose compare said
+ * "not equal" (collisions).  The two kernels are counted in no family of mc_timers.
+ */
+#define MC_DEREP_BATCH_PAIRS (1ull << 22)
+int mc_derep(mc_ctx *ctx, const uint32_t *ids, uint64_t m, int strands /* MC_STRAND_PLUS or PLUS | MINUS */,
+             uint32_t *rep /* m */, uint8_t *minus /* m; may be NULL when strands is plus only */);
+int mc_derep_profile(mc_ctx *ctx, double *out /* 5 */, int reset);
+
+/*
  * Accumulation (ClusterFactory::accumulate, ClusterFactory.cpp:637-714).
  * The bvec of Runner.cpp:342-350 is only ever shrunk after insert_finalize, so the device
  * holds one static candidate order (bin-major, length-sorted within bins) plus an alive

@@ -156,6 +156,10 @@ def gpu_lib():
         lib.mc_nw_msa_crossover.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.mc_nw_msa_crossover_profile.restype = C.c_int
         lib.mc_nw_msa_crossover_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.mc_derep.restype = C.c_int
+        lib.mc_derep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+        lib.mc_derep_profile.restype = C.c_int
+        lib.mc_derep_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         for name in ("mc_set_align_band", "mc_nw_band_plan", "mc_nw_band_profile"):
             getattr(lib, name).restype = C.c_int
         lib.mc_set_align_band.argtypes = [C.c_void_p, C.c_int]
@@ -264,6 +268,11 @@ def host_lib():
                                                                                 C.c_longlong, C.c_char_p, C.c_int]
         lib.mcl_assign_chimeras.restype = C.c_int
         lib.mcl_assign_chimeras.argtypes = lib.mcl_assign_variants.argtypes[:-2] + [C.c_char_p, C.c_longlong, C.c_char_p, C.c_int]
+        lib.mcl_derep.restype = C.c_int
+        lib.mcl_derep.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int,
+                                  C.c_longlong, C.c_char_p, C.c_int]
+        lib.mcl_derep_host.restype = C.c_int
+        lib.mcl_derep_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
         _host = lib
     return _host
 
@@ -882,6 +891,25 @@ class Engine:
         self._ck(self.lib.mc_nw_msa_crossover_profile(self.ctx, _p(out), 1 if reset else 0), "mc_nw_msa_crossover_profile")
         return float(out[0])
 
+    def derep(self, ids, strands=MC_STRAND_PLUS):
+        """mc_derep: the duplicates among the points ``ids`` (equal expanded byte strings; with
+        ``strands=MC_STRAND_PLUS | MC_STRAND_MINUS`` also a string and its minus-strand string) -> (rep uint32,
+        minus uint8): rep[i] the smallest position of the list whose point is a duplicate of ids[i]'s,
+        minus[i] 0 where the two strings are equal as written (this wins), else 1.  Exact; on the GPU only."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        rep = np.zeros(len(ids), np.uint32)
+        minus = np.zeros(len(ids), np.uint8)
+        self._ck(self.lib.mc_derep(self.ctx, _p(ids), C.c_uint64(len(ids)), int(strands), _p(rep), _p(minus)), "mc_derep")
+        return rep, minus
+
+    def derep_profile(self, reset=False):
+        """mc_derep_profile -> dict since the last reset: device ms of the fingerprint and of the compare
+        kernel, pairs compared, compare rounds, collisions (pairs whose compare said "not equal")."""
+        out = np.zeros(5)
+        self._ck(self.lib.mc_derep_profile(self.ctx, _p(out), 1 if reset else 0), "mc_derep_profile")
+        return {"fingerprint_ms": float(out[0]), "compare_ms": float(out[1]), "pairs": int(out[2]), "rounds": int(out[3]),
+                "collisions": int(out[4])}
+
     def nw_identity_raw(self, a_cat, a_off, b_cat, b_off):
         a_cat = np.ascontiguousarray(a_cat, np.uint8)
         b_cat = np.ascontiguousarray(b_cat, np.uint8)
@@ -1038,6 +1066,45 @@ def assign_files(engine, model, centres, reads, out, unassigned=None, threads=8,
     if rc != 0 or "error" in st:
         raise MCError("mcl_assign failed (%d): %s" % (rc, st.get("error", st)))
     return st
+
+
+def derep_files(engine, reads, out, table=None, both_strands=False, min_size=1, threads=8):
+    """meshclust-derep on the engine's GPU (mcl_derep: mc_derep over all reads of the FASTA or FASTQ file(s)
+    ``reads``).  ``out`` gets one FASTA record per class of identical reads -- with ``both_strands`` a read and its
+    reverse complement are identical too --, the class's first read in input order, its header extended by
+    ``;size=N``, most abundant first (ties: the earlier first read); classes of fewer than ``min_size`` reads are
+    left out.  ``table``, if given, gets one line per read in input order: read, representative, strand (+ or -),
+    size.  Returns the stats dict: reads, uniques, written, largest, minus, strands, compare_pairs, rounds,
+    collisions, phases_ms."""
+    import json
+    lib = host_lib()
+    files = [reads] if isinstance(reads, str) else list(reads)
+    arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
+    buf = C.create_string_buffer(1 << 12)
+    rc = lib.mcl_derep(engine.ctx, arr, len(files), threads, out.encode(), table.encode() if table else None,
+                       1 if both_strands else 0, int(min_size), buf, len(buf))
+    st = json.loads(buf.value.decode() or "{}")
+    if rc != 0 or "error" in st:
+        e = MCError("mcl_derep failed (%d): %s" % (rc, st.get("error", st)))
+        e.code = rc
+        raise e
+    return st
+
+
+def derep_host(codes, seq_off, ids, strands=MC_STRAND_PLUS):
+    """derep_host of libmeshclust (host/derep.hpp): mc_derep's contract computed on the CPU from the expanded
+    bytes ``codes`` and their offsets -> (rep, minus).  No fallback of ``Engine.derep``: the benchmark's host route."""
+    codes = np.ascontiguousarray(codes, np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, np.uint64)
+    ids = np.ascontiguousarray(ids, np.uint32)
+    rep = np.zeros(len(ids), np.uint32)
+    minus = np.zeros(len(ids), np.uint8)
+    if len(ids) and int(ids.max()) + 1 >= len(seq_off):
+        raise ValueError("derep_host: id out of range")
+    rc = host_lib().mcl_derep_host(_p(codes), _p(seq_off), _p(ids), C.c_uint64(len(ids)), int(strands), _p(rep), _p(minus))
+    if rc != 0:
+        raise MCError("mcl_derep_host failed (%d)" % rc)
+    return rep, minus
 
 
 class Dataset:

@@ -35,8 +35,10 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // F_NW_MSAC: the counts kernels of msa.hip (mc_nw_msa_counts), part of F_NW, for mc_nw_msa_counts_profile;
 // F_NW_BAND: the score-only launches of the width search (nwband.hip), part of F_NW, for mc_nw_band_profile;
 // F_NW_MSAS: the resolve and gather kernels of msa.hip (mc_nw_msa_sites), part of F_NW, for mc_nw_msa_sites_profile;
-// F_NW_CROSS: the kernel of crossover.hip (mc_nw_msa_crossover), part of F_NW, for mc_nw_msa_crossover_profile
-enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NW_MSAC, F_NW_BAND, F_NW_MSAS, F_NW_CROSS, F_NALL };
+// F_NW_CROSS: the kernel of crossover.hip (mc_nw_msa_crossover), part of F_NW, for mc_nw_msa_crossover_profile;
+// F_DEREP_FP / F_DEREP_CMP: the fingerprint and compare kernels of derep.hip (mc_derep), past F_NW_END: part of no
+// family of mc_timers, read by mc_derep_profile alone
+enum Family { F_KMER = 0, F_KEYS, F_PAIRS, F_SCAN, F_FINAL, F_MSHIFT, F_NW, F_LAYOUT, F_NFAM, F_NW_FWD = F_NFAM, F_NW_TB, F_NW_PU, F_NW_MSAW, F_NW_MSAR, F_NW_MSAC, F_NW_BAND, F_NW_MSAS, F_NW_CROSS, F_NW_END, F_DEREP_FP = F_NW_END, F_DEREP_CMP, F_NALL };
 
 // Classifier in the form the kernels consume (mc_classifier + the exact decision threshold).
 struct DevClassifier {
@@ -286,6 +288,10 @@ struct mc_ctx {
   std::vector<uint64_t> msa_tp_off;
   std::vector<uint8_t> msa_minus;
   std::vector<uint64_t> msa_woff, msa_row_off, msa_W;
+  // mc_derep: the call's ids and keys, a compare batch's pair records and result bytes; since the last
+  // mc_derep_profile reset: pairs compared, compare rounds, pairs that matched neither way
+  mcg::Buf dr_ids, dr_keys, dr_pairs, dr_res;
+  double dr_stat[3] = {0, 0, 0};
   // mc_update_iteration's member lists on the device and their host shadow: re-uploaded only
   // when a merge changed them (cleared when sequences are loaded: the ids were checked against n)
   mcg::Buf u_off, u_mem;
