@@ -211,6 +211,18 @@ int download_pinned(mc_ctx *c, const void *d, size_t bytes, hipStream_t s, uint8
   return MC_OK;
 }
 
+int download_to(mc_ctx *c, void *dst, const void *d, size_t bytes, size_t pinned_max) {
+  uint8_t *h = nullptr;
+  if (bytes <= pinned_max) TRY(download_pinned(c, d, bytes, c->stream, &h));
+  if (h) {
+    memcpy(dst, h, bytes);
+  } else {
+    MCG_CHECK(hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, c->stream));
+    MCG_CHECK(hipStreamSynchronize(c->stream));
+  }
+  return MC_OK;
+}
+
 }  // namespace mcg
 
 using namespace mcg;
@@ -261,8 +273,9 @@ int mc_ctx_destroy(mc_ctx *c) {
                  &c->s_c, &c->s_d, &c->s_e, &c->s_f, &c->s_g, &c->s_h, &c->s_i, &c->s_j, &c->s_k, &c->hs, &c->mag_s, &c->sumsq_s, &c->len_s, &c->ticket,
                  &c->msum, &c->ident_s, &c->al_a, &c->al_b, &c->al_out, &c->al_id, &c->ord_ids, &c->acc_out, &c->sp_words, &c->sp_keys,
                  &c->sp_scr, &c->sp_nodes, &c->sp_nn, &c->sp_q, &c->sp_err, &c->u_off, &c->u_mem, &c->nw_items, &c->nw_gran, &c->rc_seq, &c->tr_choice, &c->tr_bnd, &c->tr_ops, &c->tr_pairs, &c->tr_res, &c->tr_idx, &c->tr_dst,
-                 &c->tr_out, &c->tr_err, &c->bs_pairs, &c->bs_bnd, &c->bs_score, &c->pu_table, &c->pu_diff, &c->pu_rows, &c->pu_toff, &c->pu_roff, &c->qual, &c->pu_wtable, &c->pu_qoff, &c->msa_width, &c->msa_col, &c->msa_words, &c->msa_bw, &c->msa_rec, &c->msa_out, &c->msa_cnt, &c->msa_wcnt, &c->msa_cdiff, &c->msa_crec, &c->msa_ctgt, &c->msa_scol, &c->msa_sres, &c->msa_stgt, &c->msa_srec, &c->msa_sout, &c->msa_sq, &c->msa_xrec, &c->msa_xout, &c->hist_fwd, &c->or_runs, &c->dr_ids, &c->dr_keys, &c->dr_pairs, &c->dr_res})
+                 &c->tr_out, &c->tr_err, &c->bs_pairs, &c->bs_bnd, &c->bs_score, &c->pu_table, &c->pu_diff, &c->pu_rows, &c->pu_toff, &c->pu_roff, &c->qual, &c->pu_wtable, &c->pu_qoff, &c->hist_fwd, &c->or_runs, &c->dr_ids, &c->dr_keys, &c->dr_pairs, &c->dr_res})
     release(*b);
+  for (Buf *b : c->msa.bufs()) release(*b);
   if (c->h_scan) (void)hipHostFree(c->h_scan);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->h_dstage) (void)hipHostFree(c->h_dstage);

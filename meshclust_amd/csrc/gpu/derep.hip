@@ -202,17 +202,7 @@ int launch_derep_cmp(mc_ctx *c, const uint2 *d_pairs, uint32_t npairs, bool both
 }
 
 // `bytes` of device memory to the host, through the pinned landing buffer where it is small enough
-int fetch(mc_ctx *c, void *h, const void *d, size_t bytes) {
-  uint8_t *pin = nullptr;
-  if (bytes <= (64ull << 20)) TRY(download_pinned(c, d, bytes, c->stream, &pin));
-  if (pin) {
-    memcpy(h, pin, bytes);
-  } else {
-    MCG_CHECK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream));
-    MCG_CHECK(hipStreamSynchronize(c->stream));
-  }
-  return MC_OK;
-}
+int fetch(mc_ctx *c, void *h, const void *d, size_t bytes) { return download_to(c, h, d, bytes, 64ull << 20); }
 
 }  // namespace
 

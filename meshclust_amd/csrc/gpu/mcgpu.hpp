@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -169,6 +170,37 @@ struct CrossPair {
   uint32_t la, xnw, ynw, minus, out, pad;
 };
 
+// mc_nw_msa_begin's plan, kept until the next begin, mc_nw_msa_end or a load of
+// sequences.  Its host half: the pairs (a_minus empty: none is minus), every pair's target, word
+// count and word offset, the targets, their row offsets and block widths; tp_off / tp: every
+// target's pairs in list order (nt + 1 offsets into m pair indices).  msa_drop assigns a fresh one.
+struct MsaPlanHost {
+  bool on = false;
+  std::vector<uint32_t> a, b, targets, tof, nops, tp;
+  std::vector<uint64_t> tp_off, woff, row_off, W;
+  std::vector<uint8_t> a_minus;
+  uint64_t npairs() const { return a.size(); }
+  uint64_t ntargets() const { return targets.size(); }
+  uint64_t target_len(uint64_t t) const { return row_off[t + 1] - row_off[t] - 1; }
+  bool minus(uint64_t p) const { return !a_minus.empty() && a_minus[p]; }
+  uint64_t row_width(uint64_t s) const { return W[s < ntargets() ? s : tof[s - ntargets()]]; }  // row s of mc_nw_msa_rows
+};
+// On the device, owned by the plan and touched by no other entry; they outlive a drop and are freed
+// by mc_nw_msa_end or with the context.  width / col / words: a width and a column per pile-up row
+// (uint32), every pair's packed operation words; bw: the block widths.
+// rec / out: a render batch's row records and rendered bytes (mc_nw_msa_rows only).
+// cnt / wcnt / cdiff / crec / ctgt: a counts batch's column tables, its two difference arrays, pair
+// records and target records (mc_nw_msa_counts only).
+// scol / sres / stgt / srec / sout / sq: a call's site columns, their resolved (row, slot + 1 or 0)
+// and target records, a gather batch's pair records, alleles and weights (mc_nw_msa_sites only).
+// xrec / xout: a batch's candidate records and results (mc_nw_msa_crossover only).
+struct MsaPlan : MsaPlanHost {
+  Buf width, col, words, bw, rec, out, cnt, wcnt, cdiff, crec, ctgt, scol, sres, stgt, srec, sout, sq, xrec, xout;
+  std::array<Buf *, 19> bufs() {
+    return {&width, &col, &words, &bw, &rec, &out, &cnt, &wcnt, &cdiff, &crec, &ctgt, &scol, &sres, &stgt, &srec, &sout, &sq, &xrec, &xout};
+  }
+};
+
 // A range of one array of the device lazy introsort (split.hip): partitioned (left >= 0:
 // children left, left + 1, cut between them) or finished (fin: a sorted leaf).
 struct SplitNode {
@@ -269,25 +301,7 @@ struct mc_ctx {
   // mc_nw_qpileup_strands: the call's weight table and a batch's read offset per pair
   mcg::Buf qual, pu_wtable, pu_qoff;
   bool has_qual = false;
-  // mc_nw_msa_begin's plan, kept until the next begin, mc_nw_msa_end or a load of
-  // sequences.  On the device, owned by the plan and touched by no other entry: a width and a column
-  // per pile-up row (uint32), every pair's packed operation words.  On the host: the pairs, every
-  // pair's target, word count and word offset, the targets, their row offsets and block widths.
-  // msa_rec / msa_out: a render batch's row records and rendered bytes (mc_nw_msa_rows only).
-  // msa_tp_off / msa_tp: every target's pairs in list order (nt + 1 offsets into m pair indices).
-  // msa_cnt / msa_wcnt / msa_cdiff / msa_crec / msa_ctgt: a counts batch's column tables, its two
-  // difference arrays, pair records and target records (mc_nw_msa_counts only).
-  // msa_scol / msa_sres / msa_stgt / msa_srec / msa_sout / msa_sq: a call's site columns, their
-  // resolved (row, slot + 1 or 0) and target records, a gather batch's pair records, alleles and
-  // weights (mc_nw_msa_sites only).
-  // msa_xrec / msa_xout: a batch's candidate records and results (mc_nw_msa_crossover only).
-  bool msa_on = false;
-  mcg::Buf msa_width, msa_col, msa_words, msa_bw, msa_rec, msa_out, msa_cnt, msa_wcnt, msa_cdiff, msa_crec, msa_ctgt;
-  mcg::Buf msa_scol, msa_sres, msa_stgt, msa_srec, msa_sout, msa_sq, msa_xrec, msa_xout;
-  std::vector<uint32_t> msa_a, msa_b, msa_targets, msa_tof, msa_nops, msa_tp;
-  std::vector<uint64_t> msa_tp_off;
-  std::vector<uint8_t> msa_minus;
-  std::vector<uint64_t> msa_woff, msa_row_off, msa_W;
+  mcg::MsaPlan msa;  // mc_nw_msa_begin's plan
   // mc_derep: the call's ids and keys, a compare batch's pair records and result bytes; since the last
   // mc_derep_profile reset: pairs compared, compare rounds, pairs that matched neither way
   mcg::Buf dr_ids, dr_keys, dr_pairs, dr_res;
@@ -449,7 +463,7 @@ int launch_msa_sites(mc_ctx *c, uint64_t npairs, const MsaSitePair *d_pairs, con
 // crossover.hip (mc_nw_msa_crossover): per candidate of d_cands, none with a read above max_la bases, the
 // eight values of its two pairs' '=' bitmaps into d_out; the launch's LDS is two bitmaps of max_la bits.
 int launch_crossover(mc_ctx *c, uint32_t nc, const CrossPair *d_cands, const uint32_t *d_words, uint32_t max_la, int32_t *d_out);
-// abi_align.hip: forget mc_nw_msa_begin's plan (its device buffers stay for the next one)
+// abi_msa.hip: forget mc_nw_msa_begin's plan (its device buffers stay for the next one)
 void msa_drop(mc_ctx *c);
 
 }  // namespace mcg

@@ -260,6 +260,80 @@ def test_offsets_capacity_errors_and_state(eng, monkeypatch):
         fresh.close()
 
 
+# ---------------------------------------------------------------- 3b. a second plan owes nothing to the first
+def two_lists():
+    """-> ((a, b, minus, targets), (a, b, None, targets)): about 40 pairs on 6 targets with minus flags,
+    then about half of them in another order on 5 of the targets in another order, no flags.  In both,
+    one target has a single pair and one has none; four reads are aligned to two centres each (the
+    crossover's candidates).  Reads of 50 to 300 bases, all from msa_cases.msa()."""
+    q = A.msa()
+    p = q.pile
+    lens = [len(c) for c in q.codes]
+    of = {int(j): [k for k in range(len(q.a)) if q.b[k] == j] for j in q.targets}
+    small = [j for j in of if 3 <= len(of[j]) <= 5 and all(50 <= lens[q.a[k]] <= 300 for k in of[j])][:2]
+    ks = of[small[0]] + of[small[1]]
+    n0 = len(ks)
+    ks += of[p.contended][:15] + of[q.slots][:16] + of[q.long_target]
+    a = [int(q.a[k]) for k in ks]
+    b = [int(q.b[k]) for k in ks]
+    c0, s0, m0 = n0, n0 + 15, len(ks)  # the first contended pair, the first slots pair, the first of the four added
+    a += [a[0], a[c0], a[c0 + 1], a[s0]]
+    b += [q.slots, q.slots, small[0], p.contended]
+    assert len(of[q.long_target]) == 1 and not of[p.lonely] and all(50 <= lens[i] <= 300 for i in a) and 40 <= len(a) <= 48
+    t1 = [small[0], small[1], p.contended, q.slots, q.long_target, p.lonely]
+    minus = (np.arange(len(a)) % 3 != 2).astype(np.uint8)
+    pick = [m0 + 3, s0, m0 + 1, c0, m0 - 1] + list(range(s0 + 7, s0, -2)) + list(range(c0 + 12, c0 + 1, -2)) + [0, m0, c0 + 1, m0 + 2]
+    assert len(set(pick)) == len(pick) and not any(b[i] == small[1] for i in pick)
+    t2 = [q.slots, p.lonely, p.contended, q.long_target, small[0]]
+    u32 = lambda v: np.array(v, np.uint32)
+    return (u32(a), u32(b), minus, u32(t1)), (u32([a[i] for i in pick]), u32([b[i] for i in pick]), None, u32(t2))
+
+
+def read_everything(e, a, b, am, targets):
+    """begin, then every reader of the plan over all of it -> the arrays they return, in one list."""
+    nt, m = len(targets), len(a)
+    out = list(e.nw_msa_begin(a, b, am, targets))
+    out += e.nw_msa_rows(0, nt + m)
+    col_off, tab = e.nw_msa_counts(0, nt)
+    out += [col_off, tab]
+    cols = [np.arange(0, int(w), 3) for w in np.diff(col_off.astype(np.int64))]  # every third column of every block
+    out += e.nw_msa_sites(np.concatenate([[0], np.cumsum([len(x) for x in cols])]), np.concatenate(cols), 0, m)
+    same = [(i, j) for i in range(m) for j in range(i + 1, m) if a[i] == a[j]]
+    assert len(same) == 4
+    out.append(e.nw_msa_crossover([i for i, _ in same], [j for _, j in same]))
+    return out
+
+
+@pytest.fixture(scope="module")
+def second_alone(built):
+    """What a fresh engine gives for the second list."""
+    e = M.Engine(0)
+    try:
+        e.load_sequences(*A.msa().load_args())
+        return read_everything(e, *two_lists()[1])
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("end_between", [True, False])
+def test_second_plan_equals_a_fresh_engine(eng, second_alone, end_between, monkeypatch):
+    """A plan with minus flags, read by rows, counts, sites and crossover; then a shorter list without
+    flags on the same engine, after mc_nw_msa_end or straight away: every reader returns what a fresh
+    engine returns, so nothing of the first plan (its flags, its pairs' targets, its per-target lists)
+    is left."""
+    clean_env(monkeypatch)
+    first, second = two_lists()
+    got1 = read_everything(eng, *first)
+    assert len(got1[7]) == len(first[3]) + len(first[0]) + 1  # rows' offsets: every row of the first plan was read
+    if end_between:
+        eng.nw_msa_end()
+    got = read_everything(eng, *second)
+    assert len(got) == len(second_alone) == 13
+    for k, (x, y) in enumerate(zip(got, second_alone)):
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), k
+    assert not np.array_equal(got1[6][:64], got[6][:64])  # (the two plans' rows do differ)
+
+
 # ---------------------------------------------------------------- 4. end to end
 def msa_from_paf(paf, reads_fa, centres_fa):
     """-> the --msa file's text from a PAF's CIGARs and the two FASTA files alone (the PAF of a run
